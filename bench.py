@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: geo-embeddings/sec of the RANGE+ forward path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (encode -> stats -> attend -> finalize, i.e.
 ``load_model('RANGE+', beta=0.5)(locs)`` up to the device-resident (B,1280) float64 result) over
 one batch of synthetic queries against the synthetic ``range_db_large`` bank (N = 100 000 rows,
 SatCLIP-L40 encoder with H = 512; shapes are assumptions).  Inputs are resident in
 HBM when the timed region starts; the device->host copy of the reference's numpy contract is NOT
-in the timed region (it is measured separately and reported as ``value_host_contract``).
+in the timed region (with --full it is measured separately and reported as ``value_host_contract``).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else
+the line can carry: the parity check of the timed result against the oracle, the CPU baseline, the
+untimed extras (scan roofline, return_topk cost, host contract, opt-in bf16x3, kept-logit envelope)
+and, for N > 1, the weak-mode leg, the query-sharded control and the 2-D layouts.
+--dump-outputs DIR writes the last timed step's result to DIR (``dump_outputs``); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one rank per GPU over RCCL, the bank row-sharded (range_amd/dist.py).  ``--gpus N`` without
 WORLD_SIZE in the environment starts the N rank processes itself (fresh children of this process,
@@ -71,14 +78,19 @@ def parse():
     ap.add_argument("--shard-chunks", type=int, default=0,
                     help="query chunks of the sharded forward (0 = library default)")
     ap.add_argument("--cpu-sample", type=int, default=4096,
-                    help="queries of the same workload timed on the host for cpu_baseline (0=off)")
+                    help="--full: queries of the same workload timed on the host for cpu_baseline (0=off)")
     ap.add_argument("--sweep", default=None, nargs="?", const="0,0.25,0.5,0.75,1",
                     help="BASELINE config 5: one step = the embeddings of the batch for EVERY beta of this "
                          "comma-separated list (default 0,0.25,0.5,0.75,1): pass 1 once, two passes 2 (the "
                          "semantic and the geographic retrieval), one blend + finalize per beta; the line's "
                          "value counts queries x betas")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extras (scan roofline, host-contract rate, weak-mode leg)")
+                    help="--full: skip the untimed extras (scan roofline, host-contract rate, weak-mode leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check against the oracle, the CPU baseline and the untimed extras "
+                         "(a plain run only times the K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result to DIR/<name>.npy (a seeded sample of its rows)")
     return ap.parse_args()
 
 
@@ -124,7 +136,7 @@ def encoder_params(L, H):
 
 
 def note(msg: str) -> None:
-    """Progress on stderr (stdout carries the one JSON line): the untimed extras of a default run take a few
+    """Progress on stderr (stdout carries the one JSON line): the untimed extras of a --full run take a few
     minutes in all - the CPU baseline alone half of that - and a silent process reads as a hung one."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
@@ -276,6 +288,29 @@ def pmc_traffic(kernel, B, N, qt, ns):
             return e.get("hbm_bytes_per_launch"), \
                 f"profiles/attend_pmc.json (rocprofv3 --pmc passes of {e.get('source', '?')}; kernel sources sha256 {sha[:12]} = this checkout)", e
     return None, "no PMC entry for this workload/geometry in profiles/attend_pmc.json", None
+
+
+#: --dump-outputs writes at most this many bytes in all, over every rank
+DUMP_BYTES = 48 << 20
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: the last timed step's result as a caller receives it - (B,1280) float64, or
+    (betas,B,1280) with --sweep - as DIR/embeddings.npy, restricted to a fixed seeded sample of its
+    rows when the whole would exceed DUMP_BYTES (10 000 rows: 4 915 of them), and the sampled rows'
+    indices in the batch as DIR/embeddings_rows.npy (float64).  N > 1: each rank writes its own rows,
+    the files suffixed _rank<r>."""
+    import numpy as np
+    import torch
+    B = out.shape[-2]
+    row_bytes = out.numel() // B * out.element_size()
+    k = min(B, DUMP_BYTES // world // row_bytes)
+    idx = np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    rows = out.index_select(out.dim() - 2, torch.from_numpy(idx).to(out.device)).cpu().numpy()
+    sfx = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"embeddings{sfx}.npy"), rows)
+    np.save(os.path.join(path, f"embeddings_rows{sfx}.npy"), idx.astype(np.float64))
 
 
 #: untimed activity in front of the warm-up steps of every timed leg.  The chip lowers its clock when
@@ -512,14 +547,17 @@ def rank_main(a, rank, local, world, backend):
         note("timed leg")
     m = measure(a.scaling, a.steps, a.warmup)
     if rank == 0:
-        note(f"timed leg done: {m['B'] * world * a.steps / m['dt']:,.0f} geo-embeddings/s; parity check and untimed extras follow")
+        note(f"timed leg done: {m['B'] * world * a.steps / m['dt']:,.0f} geo-embeddings/s"
+             + ("; parity check and untimed extras follow" if a.full else ""))
     B, dt = m["B"], m["dt"]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, m["out"], rank, world)
 
-    # ---- parity of the timed result (outside the timed region): 64 of rank 0's rows against the
-    #      oracle in the reference's float32 op order and in exact float64
+    # ---- parity of the timed result (outside the timed region, --full): 64 of rank 0's rows against
+    #      the oracle in the reference's float32 op order and in exact float64
     parity = None
     parity_rows = None
-    if rank == 0:
+    if rank == 0 and a.full:
         from oracle import range_oracle as O     # checker only
         obank = O.prep_bank(*bank_arrays)
         idx = np.linspace(0, B - 1, num=min(64, B), dtype=np.int64)
@@ -553,15 +591,16 @@ def rank_main(a, rank, local, world, backend):
         if not parity["max_abs_vs_reference_f32_order"] < 1e-4:
             raise SystemExit(f"bench parity failed: {parity}")
 
-    # ---- untimed extras
+    # ---- untimed extras (--full)
     weak = None
     default_workload = betas is None and a.queries == 10_000
-    if world > 1 and a.scaling == "strong" and not a.no_extras and default_workload:
+    extras = a.full and not a.no_extras
+    if world > 1 and a.scaling == "strong" and extras and default_workload:
         mw = measure("weak", a.steps, max(1, a.warmup))
         weak = {"value": mw["B"] * world * a.steps / mw["dt"], "ms_per_step": mw["dt"] / a.steps * 1e3,
                 "queries_per_gpu": mw["B"], "comm_ms_exposed_per_step": per_step(mw["comm_ms"], a.steps)}
     control = None
-    if world > 1 and sharded and a.scaling == "strong" and not a.no_extras and default_workload:
+    if world > 1 and sharded and a.scaling == "strong" and extras and default_workload:
         # the control experiment of SURVEY.md 8(e): the same batch with the whole bank on every GPU,
         # each rank embedding its own queries end to end - no collective on the data path.  What the
         # row-sharded figure loses against it is the price of the exchange (and of scanning all
@@ -587,7 +626,7 @@ def rank_main(a, rank, local, world, backend):
                    "ms_per_step": float(tc.item()) / a.steps * 1e3, "max_abs_vs_row_sharded": agree}
         engc.close()
     layouts = None
-    if world > 2 and sharded and row_shards == world and a.scaling == "strong" and not a.no_extras and default_workload:
+    if world > 2 and sharded and row_shards == world and a.scaling == "strong" and extras and default_workload:
         # the 2-D layouts R x Q of the same job (the bank row-sharded over groups of R ranks, Q groups each
         # serving its own queries: collectives span R ranks, shards are W/R times larger) in the same
         # invocation, next to the north-star layout W x 1 that `value` reports
@@ -612,7 +651,7 @@ def rank_main(a, rank, local, world, backend):
     host_contract = None
     opt_in = None
     envelope = None
-    if world == 1 and not sharded and not a.no_extras and default_workload:
+    if world == 1 and not sharded and extras and default_workload:
         note("extras: scan roofline")
         scan = scan_roofline(eng, synth, torch, dev, N, bank)
         note("extras: return_topk cost")
@@ -712,9 +751,10 @@ def rank_main(a, rank, local, world, backend):
                 "other_ms_per_step": step_s * 1e3 - (en_ms + st_ms + att_ms) / a.steps},
             "executed_tflops": executed / step_s / 1e12,
             "reference_equivalent_tflops": B * world * n_out * N * FLOP_PAIR_REFERENCE / step_s / 1e12,
-            "parity_max_abs": parity["max_abs_vs_reference_f32_order"],
-            "parity": parity,
         }
+        if parity is not None:
+            res["parity_max_abs"] = parity["max_abs_vs_reference_f32_order"]
+            res["parity"] = parity
         if dist is not None:
             from range_amd.dist import dist_timeout_s
             be = dist.get_backend()
@@ -752,7 +792,7 @@ def rank_main(a, rank, local, world, backend):
             res["host_contract"] = host_contract
         if opt_in is not None:
             res["opt_in_bf16x3"] = opt_in
-        if world == 1 and a.cpu_sample > 0:
+        if world == 1 and a.full and a.cpu_sample > 0:
             note(f"cpu_baseline: the oracle on {usable_cpus()} host threads, {a.cpu_sample} queries (two legs)")
             res["cpu_baseline"] = cpu_baseline(weights, L, bank_arrays, a.cpu_sample, "RANGE+", a.beta)
             note("cpu_baseline done")

@@ -23,7 +23,7 @@ def _bench(extra_env, timeout=500):
         env.pop(k, None)
     t0 = time.monotonic()
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--queries", "2048", "--bank", "range_db_med", "--no-extras"],
+                        "--queries", "2048", "--bank", "range_db_med", "--full", "--no-extras"],
                        env=env, capture_output=True, text=True, timeout=timeout)
     dt = time.monotonic() - t0
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

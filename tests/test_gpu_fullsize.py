@@ -189,7 +189,7 @@ def test_bench_self_launches_two_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--bank", "range_db_med"],
+                        "--warmup", "1", "--bank", "range_db_med", "--full"],
                        env=env, cwd=REPO, capture_output=True, text=True, timeout=560)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -206,6 +206,39 @@ def test_bench_self_launches_two_ranks():
                         "--warmup", "0", "--queries", "10001"],
                        env=env, cwd=REPO, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """A plain ``bench.py`` run (no --full) times its steps and prints the line without the parity
+    check and the CPU baseline; ``--dump-outputs`` writes the last timed step's rows, which are the
+    RANGE+ forward of the bench's seeded batch."""
+    B, N = 2048, synth.BANK_ROWS["range_db_med"]
+    d = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3",
+                        "--warmup", "1", "--queries", str(B), "--bank", "range_db_med", "--dump-outputs", str(d)],
+                       cwd=REPO, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["kernels"]["attend"]["ms_per_step"] > 0
+    assert r["higher_is_better"] is True and r["unit"] == "geo-embeddings/sec" and r["dtype"] == "f32"
+    assert not {"parity", "parity_max_abs", "cpu_baseline"} & set(r)
+    assert sorted(os.listdir(d)) == ["embeddings.npy", "embeddings_rows.npy"]
+    emb, rows = np.load(d / "embeddings.npy"), np.load(d / "embeddings_rows.npy")
+    assert emb.dtype == np.float64 and emb.shape == (B, 1280) and np.array_equal(rows, np.arange(B))
+    assert np.isfinite(emb).all()
+    # 64 rows as the --full parity check takes them: e-hat against the oracle on the reference's SH
+    # polynomials (inside |lat| <= 45, where they are well conditioned), the retrieval given e-hat
+    idx = np.linspace(0, B - 1, num=64, dtype=np.int64)
+    q = synth.make_queries(B, seed=7, lat_max=90.0)[idx]
+    got = emb[idx]
+    e = O.encode(q, synth.make_encoder_weights(L, H, 256, 2, SEED), L,
+                 features=O.sh_features_faithful(q, O.load_ylm_table(), L))
+    band = np.abs(q[:, 1]) <= 45.0
+    assert band.sum() > 16 and np.abs(got[:, 1024:] - e)[band].max() < 1e-6
+    obank = O.prep_bank(*synth.make_bank(N, 2024))
+    np.testing.assert_allclose(got[:, :1024], O.retrieve64(got[:, 1024:], q, obank, "RANGE+", 0.5), rtol=0, atol=2e-5)
 
 
 def test_c5_beta_sweep_full_bank(tmp_path):

@@ -38,7 +38,7 @@ python3 $R/profiles/scan_summarize.py $O/scan $(python3 $R/range_amd/_srchash.py
 cp $O/scan_summary.json $R/profiles/scan_summary.json
 # the bench line proper, with the traffic of the passes above (stamped with this checkout's source hash)
 cp $O/attend_pmc.json $R/profiles/attend_pmc.json
-(cd $R && python3 bench.py > $O/bench.log 2> $O/bench.err)
+(cd $R && python3 bench.py --full > $O/bench.log 2> $O/bench.err)
 tail -1 $O/bench.log > $O/bench_line.json
 find $O/ks -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
 echo "bench passes done"
