@@ -1,10 +1,9 @@
 #!/bin/bash
 # Build librange_hip.so (gfx950 only) in-tree.  Usage: ./build.sh [extra hipcc flags]
 # Two translation units (retrieval engine, ridge probe) compiled side by side, then linked.
-# RANGE_LIB_OUT=<path> writes the library somewhere else (tuning sweeps build experiment variants
-# into a temporary file and load them with RANGE_LIB_PATH, never over the in-tree library).
-# The extra flags are recorded in the library (range_build_flags()): range_amd refuses to load a
-# build that carries RANGE_EXP_* timing-experiment switches.
+# RANGE_LIB_OUT=<path> writes the library somewhere else (a variant built with extra flags goes
+# into a temporary file and is loaded with RANGE_LIB_PATH, never over the in-tree library).
+# The extra flags are recorded in the library (range_build_flags()).
 set -e
 cd "$(dirname "$0")"
 out="${RANGE_LIB_OUT:-range_amd/librange_hip.so}"

@@ -64,8 +64,7 @@ typedef struct range_encoder_desc {
 int range_abi_version(void);
 const char* range_last_error(void);
 /* The extra compiler flags this library was built with (build.sh records them); "" for the
- * default build.  A build carrying RANGE_EXP_* switches is a timing experiment whose results are
- * invalid: the Python binding refuses to load it. */
+ * default build. */
 const char* range_build_flags(void);
 /* SHA-256 (hex) of the sources this library was built from (range_amd/_srchash.py; build.sh embeds
  * it): the binding refuses a library whose stamp is not the checkout's, __graft_entry__.build() rebuilds. */

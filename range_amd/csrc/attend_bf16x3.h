@@ -109,16 +109,9 @@ struct PvbB {            // the B operands of one column tile
 // every gap starts with an LDS read, an LDS-DMA or a scalar instruction - and (ii)
 // tools/check_mfma_war.py checks the generated code for exactly that (tests/test_host_cpu.py).
 __device__ __forceinline__ void mfma_bf16_a(f32x4& acc, const u32x4& a, const u32x4& b) {
-#ifdef RANGE_EXP_PVB_NOP
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0\n\ts_nop 1" : "+a"(acc) : "v"(a), "v"(b));
-#else
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-#endif
 }
-#ifndef RANGE_PVB_PF
-#define RANGE_PVB_PF 8
-#endif
-constexpr int PVB2_PF = RANGE_PVB_PF;                        // ring slots of B per wave (a power of two <= 8)
+constexpr int PVB2_PF = 8;                                   // ring slots of B per wave (a power of two <= 8)
 constexpr int PVB2_D = PVB2_PF - 1;                          // column tiles of B in flight per wave
 constexpr int PVB2_LDS_BYTES = 2 * 4 * 3 * 1024;             // A planes: 2 buffers x 4 query tiles x 3 planes
 
@@ -272,7 +265,6 @@ __global__ __launch_bounds__(256, 1) void attend_bf16x3_kernel(ScanArgs a, const
 #pragma unroll
         for (int r = 0; r < 4; ++r) e1[r] = e2[r] = ww[r] = 0.f;
         auto wop = [&](int half, int k) __attribute__((always_inline)) {
-#ifndef RANGE_EXP_PVB_NOW
             const f32x4& sv = half ? svB : svA;
             const float xa = half ? xaB : xaA;
             const int n_left = (int)(a.n_valid - (int64_t)(bn + half) * BLK);
@@ -297,7 +289,6 @@ __global__ __launch_bounds__(256, 1) void attend_bf16x3_kernel(ScanArgs a, const
             else if (k == 32 || k == 39) rb = rb - __uint_as_float(mm[k == 39] & 0xFFFF0000u);
             else if (k == 33 || k == 40) ll[k == 40] = cvt_pk_bf16(ra, rb);
             else if (k == 41) publish((gi + 1) & 1, half, hh, mm, ll);
-#endif
         };
 #pragma unroll
         for (int ct = 0; ct < 16; ++ct) {
@@ -320,22 +311,16 @@ __global__ __launch_bounds__(256, 1) void attend_bf16x3_kernel(ScanArgs a, const
 #pragma unroll
             for (int mq = 0; mq < 4; ++mq) {
                 f32x4& c = acc[16 * mq + ct];
-#ifndef RANGE_EXP_PVB_NODMA
                 const char* pn = nullptr;
                 if (mq < 3) pn = ct + PVB2_D < 16 ? addr_b(gi, ct + PVB2_D, mq) : addr_b(gi + 1, ct + PVB2_D - 16, mq);
-#endif
                 mfma_bf16_a(c, am[mq].l, b.h);
                 mfma_bf16_a(c, am[mq].m, b.m);
                 mfma_bf16_a(c, am[mq].h, b.l);
                 mfma_bf16_a(c, am[mq].m, b.h);
                 mfma_bf16_a(c, am[mq].h, b.m);
                 mfma_bf16_a(c, am[mq].h, b.h);
-#ifndef RANGE_EXP_PVB_NODMA
                 if (mq < 3) load_b1(pn, mq == 0 ? nb.h : mq == 1 ? nb.m : nb.l);
                 else asm volatile("s_nop 0");                 // (no vector ALU directly behind an MFMA)
-#else
-                asm volatile("s_nop 0");
-#endif
                 if (ct >= 4) {                               // two statements of the next group's weights
                     const int half = ct >= 10, k = 8 * (ct - (half ? 10 : 4)) + 2 * mq;
                     __builtin_amdgcn_sched_barrier(0);

@@ -151,11 +151,7 @@ __device__ __forceinline__ void decode_block(const ScanArgs& a, int& split, int&
     const int b = blockIdx.x;
     const int x = b & 7, j = b >> 3;
     const int q = total >> 3, r = total & 7;
-#ifdef RANGE_EXP_P2_SCATTER     // timing experiment: workgroups of an XCD on unrelated splits (no sharing of V in its L2)
-    const int item = (int)(((int64_t)b * 997) % total);
-#else
     const int item = x * q + (x < r ? x : r) + j;
-#endif
     split = item / a.n_qtiles;
     qt = item - split * a.n_qtiles;
 }
@@ -262,11 +258,7 @@ __device__ __forceinline__ void qk_mfma(const char* kt, const KFirst& first, con
     for (int s = 0; s < 16; ++s) {
         const f32x4 ka = kn;
         kn = kn2;
-#ifdef RANGE_EXP_P1_NOLDS
-        if (s < 14) kn2 = ka;
-#else
         if (s < 14) kn2 = *reinterpret_cast<const f32x4*>(kt + ka_.b[(s + 2) & 3] + 256 * ((s + 2) >> 2));
-#endif
         if (s == 0) mfma_v_first(c.a0, ka.x, f.q[s].x);
         else mfma_v(c.a0, ka.x, f.q[s].x);
         mfma_v(c.a0, ka.y, f.q[s].y);
@@ -357,14 +349,7 @@ __device__ __forceinline__ void issue_v_half(const float* values, int64_t row0, 
 
 // wait for all but the n youngest vector-memory operations of this wave, then workgroup barrier.
 // One asm statement with a memory clobber: no LDS access may be moved across it by the compiler.
-// RANGE_EXP_NOBAR / RANGE_EXP_NODMA / RANGE_EXP_NOLDS: tuning experiments only (./build.sh -D...):
-// they drop the barriers / the in-loop LDS-DMA issue / the V operand reads of pass 2 to price
-// each of them; the results of such a build are garbage.
-#ifdef RANGE_EXP_NOBAR
-#define RANGE_WAIT_BARRIER(n) asm volatile("s_waitcnt vmcnt(" #n ") lgkmcnt(0)" ::: "memory")
-#else
 #define RANGE_WAIT_BARRIER(n) asm volatile("s_waitcnt vmcnt(" #n ") lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#endif
 
 // Diagnostic build only (attend_kernel<GEO, true>, never on the product path): s_memtime stamps
 // around the two parts of a wait so that their cycles can be summed per wave.
@@ -466,13 +451,11 @@ __global__ __launch_bounds__(256) void scan_stats_kernel(ScanArgs a) {
     int slot = 0;
     for (int t = 0; t < nb; ++t) {
         RANGE_WAIT_BARRIER(0);
-#ifndef RANGE_EXP_P1_NODMA
         if (t + 1 < nb) {
             const int s2 = slot ^ 1;
             issue_k_tile(a.keys, a.xyz4, (int64_t)(b0 + t + 1) * BLK, kring_lds + s2 * KT_BYTES,
                          xring_lds + s2 * 256, wave, lane, swz);
         }
-#endif
         QKAcc c;
         qk_mfma<GEO>(smem + slot * KT_BYTES,
                      qk_first_reads<GEO>(smem + slot * KT_BYTES, smem + 2 * KT_BYTES + slot * 256, kaddr),
@@ -483,12 +466,8 @@ __global__ __launch_bounds__(256) void scan_stats_kernel(ScanArgs a) {
         if (a.logits)   // keep the tile for pass 2 (the barrier's vmcnt(0) also covers this store)
             // (non-temporal: 4 GB per 10^4 x 10^5 launch that nobody reads before pass 2 - measured
             // three A/B pairs, 10 000 queries: pass 1 3.937 -> 3.916 ms, the pass 2 behind it 14.690 ->
-            // 14.616 ms; -DRANGE_EXP_P1_TSTORE restores the default policy)
-#ifdef RANGE_EXP_P1_TSTORE
-            *reinterpret_cast<f32x4*>(a.logits + logit_tile((int64_t)qt + a.qt_offset, a.n_blocks, b0 + t, wave) + 4 * lane) = ss;
-#else
+            // 14.616 ms)
             __builtin_nontemporal_store(ss, reinterpret_cast<f32x4*>(a.logits + logit_tile((int64_t)qt + a.qt_offset, a.n_blocks, b0 + t, wave) + 4 * lane));
-#endif
         // statistics of this tile.  Only the bank's last block can hold pad rows: every other
         // tile takes the unmasked form
         const int64_t row0 = (int64_t)(b0 + t) * BLK;
@@ -505,7 +484,6 @@ __global__ __launch_bounds__(256) void scan_stats_kernel(ScanArgs a) {
             if (a.rowmax)
                 smax = fmaxf(smax, fmaxf(fmaxf(ok[0] ? ss[0] : -INFINITY, ok[1] ? ss[1] : -INFINITY),
                                          fmaxf(ok[2] ? ss[2] : -INFINITY, ok[3] ? ss[3] : -INFINITY)));
-#ifndef RANGE_EXP_P1_NOVALU
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float p1 = __builtin_amdgcn_exp2f(fmaf(ss[r], a.k_sem, nm1));
@@ -515,9 +493,6 @@ __global__ __launch_bounds__(256) void scan_stats_kernel(ScanArgs a) {
                     l2 += ok[r] ? p2 : 0.f;
                 }
             }
-#else
-            l1 += ss[0] + ss[3]; if (GEO) l2 += sg[1];
-#endif
         };
         if (n_here == BLK) tile_stats(std::false_type{});
         else tile_stats(std::true_type{});
@@ -917,12 +892,8 @@ __device__ __forceinline__ void pv_steps(const float* vslot, float w0, float w1,
     for (int T = 0; T < 14; ++T) {
         // lane (j,g) reads V[row 2g+rr][64T + 4j .. +3]: one ds_read_b128 feeds 4 accumulator
         // tiles; the reads of step T+2 sit in front of step T's 8 MFMAs (512 cycles of cover)
-#ifdef RANGE_EXP_NOLDS
-        const f32x4 m0 = v1, m1 = v0;
-#else
         const f32x4 m0 = *reinterpret_cast<const f32x4*>(base + 64 * (T + 2));
         const f32x4 m1 = *reinterpret_cast<const f32x4*>(base + VAL_DIM + 64 * (T + 2));
-#endif
         RANGE_PV_MFMA(4 * T + 0, w0, v0.x, 8 * T + 0);
         RANGE_PV_MFMA(4 * T + 1, w0, v0.y, 8 * T + 1);
         RANGE_PV_MFMA(4 * T + 2, w0, v0.z, 8 * T + 2);
@@ -1003,11 +974,8 @@ struct SegWalk {
 constexpr int ATTEND_LDS_BYTES = (3 * 8 * VAL_DIM + 2 * BLK * KEY_DIM + 2 * 64) * 4;
 // pass 1: workgroups per CU (4 = what the 33 KB of LDS allow; fewer by padding the allocation:
 // measured 3 and 2 per CU slower, tools/README.md)
-#ifndef RANGE_P1_WG_PER_CU
-#define RANGE_P1_WG_PER_CU 4
-#endif
-constexpr int SCAN_LDS_BYTES = RANGE_P1_WG_PER_CU >= 4 ? (2 * BLK * KEY_DIM + 2 * 64) * 4
-                                                       : (160 * 1024 / RANGE_P1_WG_PER_CU) / 256 * 256 - 512;
+constexpr int P1_WG_PER_CU = 4;
+constexpr int SCAN_LDS_BYTES = (2 * BLK * KEY_DIM + 2 * 64) * 4;
 
 template <bool GEO, bool DIAG = false>
 __global__ __launch_bounds__(256, 1) void attend_kernel(ScanArgs a) {
@@ -1243,12 +1211,6 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4;
-#ifdef RANGE_EXP_P2_STAMPS
-    // timing build: s_memtime (shader clocks) / s_memrealtime (100 MHz) at entry, loop start, loop
-    // end, stores issued, stores done + the CU this workgroup ran on (tools/pass2_stamps.py)
-    unsigned long long st_c[5], st_r[5];
-    st_c[0] = stamp(); st_r[0] = __builtin_amdgcn_s_memrealtime();
-#endif
     SegWalk walk;
     walk.init(a);
     int qt, b0, b1;
@@ -1321,9 +1283,6 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
     carry.v0a = carry.v1a = carry.v0b = carry.v1b = f32x4{0.f, 0.f, 0.f, 0.f};
     carry.w0 = carry.w1 = 0.f;
     const int b_last = b1 - 1;
-#ifdef RANGE_EXP_P2_STAMPS
-    st_c[1] = stamp(); st_r[1] = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int t = 0; t < nb; ++t) {
         const int vs1 = vs == 2 ? 0 : vs + 1;
         const int vs2 = vs1 == 2 ? 0 : vs1 + 1;
@@ -1343,13 +1302,11 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
             pv_exec_carry(acc, carry);                       // last step of the previous half
             pv_steps(vring + vs * 8 * VAL_DIM, w_cur[0], w_cur[1], s0, s1, acc, lane, carry,
                      [&](int h) __attribute__((always_inline)) {
-#ifndef RANGE_EXP_NODMA
                          if (h % 14 == 3) {                  // 8 pieces: V half 2t+2
                              const int ii = h / 14;
                              if ((ii & 3) == 0) dma_group_begin(vdst_e + (ii >> 2) * 4096);
                              dma_b128_q(vsrc1 + (ii >> 2) * VAL_DIM, vvoff, ii & 3);
                          }
-#endif
                      });
         }
         // ---- half 2t+1 : leaves E(t) = 8 operations in flight
@@ -1368,13 +1325,8 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
         const int n_left1 = n_left - (t + 1) * BLK;
         pv_steps(vring + vs1 * 8 * VAL_DIM, w_cur[2], w_cur[3], s0, s1, acc, lane, carry,
                 [&](int h) __attribute__((always_inline)) {
-#ifdef RANGE_EXP_NODMA
-                    if (false) {
-                        const int ii = 0;
-#else
                     if ((h & 7) == 3) {
                         const int ii = h >> 3;               // 10 pieces: V half 2t+3, S/X tile t+2
-#endif
                         if (ii < 8) {
                             if ((ii & 3) == 0) dma_group_begin(vdst_o + (ii >> 2) * 4096);
                             dma_b128_q(vsrc1 + (8 + (ii >> 2)) * VAL_DIM, vvoff, ii & 3);
@@ -1410,9 +1362,6 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
     if (nb > 0) pv_exec_carry(acc, carry);   // last step of the last half
     // the clamped prefetches of the last iterations are still in flight into this workgroup's LDS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef RANGE_EXP_P2_STAMPS
-    st_c[2] = stamp(); st_r[2] = __builtin_amdgcn_s_memrealtime();
-#endif
 
     acc_fence(acc);
     // accumulator tile 4T+c, register r, lane (j,g)  ->  out[query 4g+r of this wave][64T + 4j + c]
@@ -1431,19 +1380,6 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
         }
     }
     }   // segments
-#ifdef RANGE_EXP_P2_STAMPS
-    st_c[3] = stamp(); st_r[3] = __builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    st_c[4] = stamp(); st_r[4] = __builtin_amdgcn_s_memrealtime();
-    if (a.diag && threadIdx.x == 0) {
-        unsigned long long* d = a.diag + (size_t)blockIdx.x * 16;
-        for (int i = 0; i < 5; ++i) { d[i] = st_c[i]; d[5 + i] = st_r[i]; }
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        d[10] = hw; d[11] = xcc & 0xf; d[12] = (unsigned long long)(a.sk_groups > 0 ? ((int64_t)a.n_qtiles * a.n_blocks) / a.sk_groups : a.n_blocks / a.n_splits);
-    }
-#endif
 }
 
 

@@ -28,7 +28,7 @@
 //     be left to place them.  What bounds the kernel (round 3, profiles/NOTES.md A.2): the 16-query
 //     loop streams its 513 MB in 80 us = 6.4 TB/s, the rate a plain copy reaches on this chip - it
 //     is HBM-bound, and timing builds without the exchange, without the logit MFMAs, without the
-//     LDS reads of V (-DRANGE_EXP_AS_NOEXCH / _NOLOGITS / _NOVREAD, results invalid) take the same
+//     LDS reads of V (results invalid) take the same
 //     time to the microsecond.  The waves do not wait in their vmcnt waits (1 us of 80) but at the
 //     ISSUE of the next LDS-DMA request, which blocks while the memory pipeline is full - stamps
 //     around the waits alone read as "compute-bound".  The rest of the kernel's 93-99 us: ~6 us
@@ -70,12 +70,7 @@ constexpr int AS_OFF_XBUF = 4 * AS_WAVE_LDS;               // partial logit tile
 constexpr int as_lds_bytes(int nq) { return AS_OFF_XBUF + 2 * nq * 4 * 1024; }
 
 // the bank is streamed once per launch: non-temporal requests (measured, 16 queries against
-// range_db_large: 99 -> 94 us per call; RANGE_EXP_AS_TEMPORAL restores the default policy)
-#ifdef RANGE_EXP_AS_TEMPORAL
-#define AS_DMA dma_b128
-#else
-#define AS_DMA dma_b128_nt
-#endif
+// range_db_large: 99 -> 94 us per call)
 template <bool GEO, int NQ>
 __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
         const int slot = t & 1;
         const float* ksrc = a.keys + (int64_t)(b0 + tt) * BLK * KEY_DIM;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) AS_DMA(ksrc, kvoff[i], wl_lds + AS_OFF_K + slot * AS_K_BYTES + i * 1024);
+        for (int i = 0; i < 4; ++i) dma_b128_nt(ksrc, kvoff[i], wl_lds + AS_OFF_K + slot * AS_K_BYTES + i * 1024);
         if (GEO) dma_b32(a.xyz4 + (int64_t)(b0 + tt) * BLK * 4, (uint32_t)(lane << 2), wl_lds + AS_OFF_X + slot * AS_X_BYTES);
     };
     const uint32_t vvoff = (uint32_t)(wave * 1024 + (lane << 4));
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
         const uint32_t dst = wl_lds + (uint32_t)(v % AS_VSLOTS) * AS_V_BYTES;
         const float* vsrc = a.values + ((int64_t)(b0 + tt) * BLK + 8 * h) * VAL_DIM;
 #pragma unroll
-        for (int r8 = 0; r8 < 8; ++r8) AS_DMA(vsrc + r8 * VAL_DIM, vvoff, dst + r8 * 1024);
+        for (int r8 = 0; r8 < 8; ++r8) dma_b128_nt(vsrc + r8 * VAL_DIM, vvoff, dst + r8 * 1024);
     };
     // one row of the same request (RANGE_AS_SPREAD: the eight requests of a half go out between its
     // MFMAs, one per 16, instead of in a burst in front of them - a burst into a full memory
@@ -145,13 +140,9 @@ __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
         const int tt = t < nb ? t : nb - 1;
         const uint32_t dst = wl_lds + (uint32_t)(v % AS_VSLOTS) * AS_V_BYTES;
         const float* vsrc = a.values + ((int64_t)(b0 + tt) * BLK + 8 * h) * VAL_DIM;
-        AS_DMA(vsrc + r8 * VAL_DIM, vvoff, dst + r8 * 1024);
+        dma_b128_nt(vsrc + r8 * VAL_DIM, vvoff, dst + r8 * 1024);
     };
-#ifdef RANGE_EXP_AS_BURST
-    constexpr bool SPREAD = false;
-#else
     constexpr bool SPREAD = NQ * (GEO ? 2 : 1) > 2;     // (the asm-MFMA kernel: program order is issue order)
-#endif
     constexpr int OPS_KX = GEO ? 5 : 4, OPS_V = 8;
     // the order of the steady state: [K X (t+2)] after the logits of t, [V (t+1, 1)] after the first
     // half of t, [V (t+2, 0)] after its second half
@@ -227,9 +218,6 @@ __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
 #pragma unroll
             for (int nq = 0; nq < NQ; ++nq) {
                 c[nq] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef RANGE_EXP_AS_NOLOGITS
-                c[nq] = kf[0] + kf[1] + kf[2] + kf[3];
-#else
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     c[nq] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s].x, qf[nq][s].x, c[nq], 0, 0, 0);
@@ -237,33 +225,24 @@ __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
                     c[nq] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s].z, qf[nq][s].z, c[nq], 0, 0, 0);
                     c[nq] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s].w, qf[nq][s].w, c[nq], 0, 0, 0);
                 }
-#endif
                 cg[nq] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (GEO) cg[nq] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa, xqv[nq], cg[nq], 0, 0, 0);
             }
         }
         // ---- the four k-slices meet: partial tiles through LDS, summed in a fixed order
         f32x4* xb = xbuf + (t & 1) * (NQ * 256);
-#ifndef RANGE_EXP_AS_NOEXCH      // (timing experiments: results invalid)
 #pragma unroll
         for (int nq = 0; nq < NQ; ++nq) xb[(nq * 4 + wave) * 64 + lane] = c[nq];
-#ifndef RANGE_EXP_AS_NOBAR
         __syncthreads();
-#endif
-#endif
         // ---- un-normalised weights of both heads (pad rows of the bank's last block: 0)
         const uint32_t row0 = (uint32_t)(b0 + t) * BLK;
         float p1[NQ][4], p2[NQ][4];
 #pragma unroll
         for (int nq = 0; nq < NQ; ++nq) {
-#ifdef RANGE_EXP_AS_NOEXCH
-            f32x4 sv = c[nq];
-#else
             f32x4 sv = xb[(nq * 4 + 0) * 64 + lane];
             sv += xb[(nq * 4 + 1) * 64 + lane];
             sv += xb[(nq * 4 + 2) * 64 + lane];
             sv += xb[(nq * 4 + 3) * 64 + lane];
-#endif
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const bool ok = row0 + prow[r] < (uint32_t)a.n_valid;
@@ -289,11 +268,7 @@ __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
-#ifdef RANGE_EXP_AS_NOVREAD
-                for (int gg = 0; gg < 4; ++gg) vb[rr][gg] = f32x4{(float)t, (float)h, (float)rr, (float)gg};
-#else
                 for (int gg = 0; gg < 4; ++gg) vb[rr][gg] = *reinterpret_cast<const f32x4*>(vt + rr * 1024 + gg * 256);
-#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr)

@@ -83,8 +83,8 @@ struct EncArgs {
     int32_t n_parts2;
     int32_t part2_cols;
     int32_t rest_from;
-    // ... and, for a few tiles, the LAST layer over 4 parts of 64 outputs per tile (MODE 4: raw
-    // outputs + bias to e3); encoder_norm_kernel then normalises and writes the results
+    // ... and, in encoder_tile_kernel, the LAST layer over 4 parts of 64 outputs per tile (MODE 4: raw
+    // outputs + bias to e3); encoder_norm_query then normalises and writes the results
     double* e3;                 // (ceil(B/16)*16, 256) f64
     double* h1a;                // encoder_tile_kernel: the ACTIVATED first layer of the tile (16, H) f64, or null
     // encoder_tile_kernel (one 16-query tile, one launch): 4 arrival counters, 64 words apart; zero
@@ -227,12 +227,6 @@ __device__ __forceinline__ void store_act(double* lds, const double* bias, doubl
     }
 }
 
-#ifdef RANGE_EXP_ENC_STAMPS   // tuning only: phase stamps of workgroup 0 / thread 0 behind e3's rows (100 MHz counter)
-#define ENC_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && a.e3) reinterpret_cast<unsigned long long*>(a.e3 + ((a.B + 15) / 16) * 16 * ENC_EMBED)[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define ENC_STAMP(i) do { } while (0)
-#endif
-
 // NT = H / 64.  NW waves per workgroup (4 or 16) share the H/16 n-tiles of 16 hidden columns:
 // NTW = 4*NT/NW per wave (and 16/NW of the 16 output n-tiles).  Sixteen waves (four per SIMD)
 // are what the float64 MFMA pipe wants (tools/micro/mfma_f64_peak.hip: 36 TFLOP/s with 1-2 waves
@@ -327,11 +321,7 @@ __device__ __forceinline__ void encoder_body(const EncArgs& a, int64_t q0, char*
         const int kp1 = a.slot_base[s_last];
         __syncthreads();   // previous round's fragment reads are done
         const int slot = s_first + gslot;
-#ifdef RANGE_EXP_ENC_NOGEN      // (timing experiment: no feature generation at all)
-        if (false) {
-#else
         if (a.sh_desc) {
-#endif
             // the generated functions Yl{l}_m{m} of this slot's orders, in the reference's order of
             // operations: every product and every sum rounded on its own (no fused multiply-add),
             // the terms of a sum left to right; degrees l = m + gsub, m + gsub + NSUB, ...
@@ -392,11 +382,7 @@ __device__ __forceinline__ void encoder_body(const EncArgs& a, int64_t q0, char*
                 if (gsub == 0)
                     for (int pos = pos_m; pos < end; ++pos) lds[act_addr<QT>(gq, pos)] = 0.0;
             }
-#ifdef RANGE_EXP_ENC_NOGEN
-        } else if (false) {
-#else
         } else if (gslot < ENC_SLOTS_PER_ROUND && slot < s_last) {
-#endif
             int pos = a.slot_base[slot] - kp0;
             const int end = a.slot_base[slot + 1] - kp0;
             const int m_a = slot;
@@ -474,7 +460,7 @@ __device__ __forceinline__ void encoder_body(const EncArgs& a, int64_t q0, char*
     }
     if (MODE == 4) {
         // 64 outputs of the last layer (Identity activation, location_encoder.py:95-96, 112): one n-tile
-        // per wave (4 waves), raw value + bias to e3; the norm follows in encoder_norm_kernel
+        // per wave (4 waves), raw value + bias to e3; the norm follows in encoder_norm_query
         __syncthreads();
         const int kpH4 = a.H >> 3;
         f64x4 ae4[1][1] = {{f64x4{0, 0, 0, 0}}};
@@ -506,7 +492,6 @@ __device__ __forceinline__ void encoder_body(const EncArgs& a, int64_t q0, char*
     if (MODE == 3) {
         // the part's columns of the second layer: h2 = sin(acc + b) (location_encoder.py:147-150, w0 = 1)
         __syncthreads();
-        ENC_STAMP(10);
         const int kpH3 = a.H >> 3;
         // (encoder_tile_kernel runs this with 16 waves for NW = 4: 4 quarters of K per n-tile, as in MODE 4)
         const int KS = (NTW == 1 && 16 * a.H + 3 * NW * 256 <= a.lds_main_doubles && (int)(blockDim.x >> 6) >= 4 * NW && (kpH3 & 3) == 0) ? 4 : 1;
@@ -523,7 +508,6 @@ __device__ __forceinline__ void encoder_body(const EncArgs& a, int64_t q0, char*
             if (kq > 0) return;
             for (int kk = 0; kk < KS - 1; ++kk) acc[0][0] += px[(kk * NW + wn) * 64 + lane];
         }
-        ENC_STAMP(11);
 #pragma unroll
         for (int i = 0; i < NTW; ++i) {
             const int n = part * a.part2_cols + (wn * NTW + i) * 16 + (lane & 15);
@@ -649,14 +633,6 @@ __global__ __launch_bounds__(NTP * 256, 1) void encoder_l2_part_kernel(EncArgs a
     encoder_body<NTP, 4 * NTP, 1, 3>(a, (int64_t)tile * 16, smem, part);
 }
 
-// last layer per (16-query tile, part of 64 outputs): 4 waves, one n-tile each (NT = H / 64 only
-// sizes the body's unused hidden-layer registers: 4 keeps them minimal)
-__global__ __launch_bounds__(256, 1) void encoder_l3_part_kernel(EncArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tile = blockIdx.x >> 2, part = blockIdx.x & 3;
-    encoder_body<4, 4, 1, 4>(a, (int64_t)tile * 16, smem, part);
-}
-
 // e = e3 / |e3| (range.py:212), its float32 copy, the raw output if asked for, and the query's unit
 // vector (float64 trig, then .float(): range.py:225-231, utils.py:11-16).  One wave per query.
 __device__ __forceinline__ void encoder_norm_query(const EncArgs& a, int64_t q, int lane) {
@@ -681,17 +657,13 @@ __device__ __forceinline__ void encoder_norm_query(const EncArgs& a, int64_t q, 
         *reinterpret_cast<float4*>(a.xq + q * 4) = make_float4((float)(cl * cos(lon)), (float)(cl * sin(lon)), (float)sin(lat), 0.f);
     }
 }
-__global__ __launch_bounds__(256) void encoder_norm_kernel(EncArgs a) {
-    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q < a.B) encoder_norm_query(a, q, threadIdx.x & 63);
-}
 
 // ONE launch for a FEW 16-query tiles (the latency regime: up to 512 queries), each tile on its own
 // workgroups.  As separate launches the
 // small-batch encoder costs ~110 us: the first layer's part kernel 33 us, then ONE workgroup's chain
 // over the rest (90 us) - and every further launch that would spread that chain costs 10-20 us of its
 // own (dispatch + 4-6 us before a kernel's first memory access returns).  Here the workgroups of the
-// first layer stay and meet at counters (phase stamps of a -DRANGE_EXP_ENC_STAMPS build, round 3: the
+// first layer stay and meet at counters (phase stamps, round 3: the
 // first layer 12.5 us; summing + activating its 16 x H outputs 58 us when 256 threads of a workgroup
 // did it alone - one memory round trip and one float64 sin per element and thread):
 //   phase 1  all workgroups (n_parts x n_kparts): first layer, one column part x one K range (MODE 1)
@@ -772,13 +744,11 @@ __global__ __launch_bounds__(ENC_PART_WAVES * 64, 1) void encoder_tile_kernel(En
     const int64_t q0 = (int64_t)tile * 16;
     const int64_t rows = ((a.B + 15) / 16) * 16;
     uint32_t* sync = a.sync + tile * 256;
-    ENC_STAMP(0);
     {
         EncArgs a1 = a;
         a1.h1a = nullptr;
         encoder_body<NTP, NWP, 1, 1, ENC_PART_WAVES>(a1, q0, smem, part, kpart);
     }
-    ENC_STAMP(1);
     // ---- h1a = sin(30 (sum of the K parts + b)) (location_encoder.py:119, 147-150): one element per thread
     // The first K = max(workgroups of any later phase) workgroups stay to the end and meet at every
     // counter, whether or not a phase has work for them (narrow encoders: 2 workgroups activate, 2 run
@@ -798,7 +768,6 @@ __global__ __launch_bounds__(ENC_PART_WAVES * 64, 1) void encoder_tile_kernel(En
         }                                                                                       \
     } while (0)
     ENC_HANDOFF(sync, n_wg, K, b < K);
-    ENC_STAMP(2);
     for (int blk = b; blk < n_act; blk += K) {
         const int e = blk * (int)blockDim.x + (int)threadIdx.x;
         if (e < 16 * a.H) {
@@ -809,10 +778,8 @@ __global__ __launch_bounds__(ENC_PART_WAVES * 64, 1) void encoder_tile_kernel(En
             st_xwg(a.h1a + at, sin(30.0 * (v + a.bias[0][k])));
         }
     }
-    ENC_STAMP(3);
     // ---- second layer on the first n_parts2 workgroups
     ENC_HANDOFF(sync + 64, K, K, true);
-    ENC_STAMP(4);
     // (parts of 64 columns with K split four ways where a tile has >= H / 64 workgroups; wider parts -
     // 128 or 256 columns, one n-tile per wave over the whole K - where it has fewer: the host chooses)
     for (int part = b; part < a.n_parts2; part += K) {
@@ -820,12 +787,9 @@ __global__ __launch_bounds__(ENC_PART_WAVES * 64, 1) void encoder_tile_kernel(En
         else if (a.part2_cols == 128) encoder_body<2, 8, 1, 3>(a, q0, smem, part, 0, part != b);
         else encoder_body<4, 16, 1, 3>(a, q0, smem, part, 0, part != b);
     }
-    ENC_STAMP(5);
     // ---- last layer on workgroups 0..3
     ENC_HANDOFF(sync + 128, K, K, true);
-    ENC_STAMP(6);
     for (int part = b; part < 4; part += K) encoder_body<4, 4, 1, 4>(a, q0, smem, part, 0, part != b);
-    ENC_STAMP(7);
     // ---- norm on workgroup 0: a wave per query
     ENC_HANDOFF(sync + 192, K, 1, b == 0);
 #undef ENC_HANDOFF
@@ -833,7 +797,6 @@ __global__ __launch_bounds__(ENC_PART_WAVES * 64, 1) void encoder_tile_kernel(En
         const int64_t q = q0 + (threadIdx.x >> 6);
         if (q < a.B) encoder_norm_query(a, q, threadIdx.x & 63);
     }
-    ENC_STAMP(8);
 }
 
 template <int NT, int NW>

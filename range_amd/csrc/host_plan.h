@@ -175,8 +175,8 @@ inline std::vector<double> pad_weights(const double* W, int n_out, int k_in, int
 
 // Query ranges of the numpy contract's pass 2 (range_forward_host): the batch in parts, the tail parts
 // of the given nominal sizes (the last ones shortest: their copies are what the caller waits for), cuts
-// rounded UP to a query tile, never past the batch and never backwards - whatever `tail` holds
-// (RANGE_HOST_PARTS).  Returns the cut positions, first 0 and last B.
+// rounded UP to a query tile, never past the batch and never backwards - whatever `tail` holds.
+// Returns the cut positions, first 0 and last B.
 inline std::vector<int64_t> host_part_cuts(int64_t B, const std::vector<int64_t>& tail, int64_t tile) {
     std::vector<int64_t> cuts{0};
     int64_t rest = 0;

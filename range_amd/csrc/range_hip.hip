@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -26,25 +25,6 @@
 
 using namespace range_hip;
 using namespace range_host;
-
-// waves per encoder workgroup when the hidden width is a multiple of 256 (4 or 16)
-#ifndef RANGE_ENC_WAVES
-#define RANGE_ENC_WAVES 16
-#endif
-// top-k batches up to this size keep per-lane lists inside pass 1 (scan_stats_kernel<.., true>),
-// larger ones select from the kept logits.  Measured (tools/topk_total_time.py): the selection
-// wins at every batch size, so the in-scan lists only serve contexts that cannot keep logits.
-#ifndef RANGE_TOPK_INSCAN_MAX
-#define RANGE_TOPK_INSCAN_MAX 0
-#endif
-// range_topk_stream: query groups (of 16) sharing one pass over the keys (0 = by batch size:
-// 1 group up to 16 queries, 2 up to 32, 4 beyond), and the depth of the per-lane lists
-#ifndef RANGE_TOPKS_GROUPS
-#define RANGE_TOPKS_GROUPS 0
-#endif
-#ifndef RANGE_TOPKS_LIST
-#define RANGE_TOPKS_LIST 4
-#endif
 
 struct range_ctx {
     int device = 0;
@@ -79,14 +59,10 @@ struct range_ctx {
     bool allow_keep = true;   // RANGE_KEEP_LOGITS=0 in the environment: never keep (pass 2 recomputes)
     bool warned_no_keep = false;
     bool enc_split = true;    // RANGE_ENC_SPLIT=0: small batches use the one-kernel encoder too
-    bool enc_split2 = true;   // RANGE_ENC_SPLIT2=0: ... without the second layer's own split
-    bool enc_split3 = false;  // RANGE_ENC_SPLIT3=1: the last layer split too for up to 8 tiles (measured slower: see launch_encoder_split)
-    bool enc_tail_split = true;   // RANGE_ENC_TAIL=0: the last partial round of a large batch as 16-query workgroups
     DevBuf<int32_t> ws_cand_idx;
     DevBuf<unsigned long long> ws_cand_keys;
     DevBuf<float> ws_cand_dmax;
     DevBuf<int32_t> ws_exact_count;   // queries range_topk_stream recomputed by brute force
-    int topks_groups = RANGE_TOPKS_GROUPS;   // RANGE_TOPKS_GROUPS in the environment overrides
     bool topks_force_exact = false;          // RANGE_TOPKS_FORCE_EXACT=1: tests of the fallback
     bool topks_bf16 = true;                  // RANGE_TOPKS_KEYS=f32: stream the float32 keys (no prefilter)
     bool topks_fused = true;                 // RANGE_TOPKS_FUSED=0: the merge as a second launch at every batch size (A/B)
@@ -101,7 +77,6 @@ struct range_ctx {
     DevBuf<float> ws_tg_qscale;              // ... and their scales
     DevBuf<uint32_t> ws_tg_cnt, ws_tg_ovf;
     DevBuf<uint2> ws_tg_cand;                  // candidate lists: lengths (B, lists), rows (B, lists, TG_CAP_L); overflow flags (B)
-    int p2_splits_forced = 0;                // RANGE_P2_SPLITS=n: pass 2 with n bank splits (tuning)
     bool small_forward = true;               // RANGE_SMALL_FORWARD=0: batches of <= 32 queries take the two-pass kernels too (A/B)
     DevBuf<float> ws_small_o, ws_small_z;    // attend_small_kernel: per-workgroup partial products / weight sums
     DevBuf<uint32_t> ws_read_sink;           // range_stream_read_timed: one word per workgroup
@@ -119,19 +94,14 @@ struct range_ctx {
     uint32_t* h_async_err = nullptr;
     uint32_t* d_async_err = nullptr;
     bool enc_fused = true;          // RANGE_ENC_FUSED=0: up to 16 queries take the separate small-batch kernels
-    bool enc_fused_mid = true;      // RANGE_ENC_FUSED_MID=0: 513 .. 2 048 queries as three launches (A/B)
-    int enc_fused_mid_min_wg = 2;   // RANGE_ENC_FUSED_MID_MIN_WG=n: ... one launch while a tile gets >= n workgroups (tuning)
     int last_qtiles = 0, last_splits = 0;
     bool p2_streamk = true;         // RANGE_P2_STREAMK=0: pass 2 as one workgroup per (bank split, query tile) (A/B)
-    int p2_col_rows = 16384;        // RANGE_P2_COL_ROWS=n: largest bank column of the stream-K walk (rows; tuning)
-    int p2_streamk_rows = 50000;    // RANGE_P2_STREAMK_ROWS=n: banks / shards up to n rows take the stream-K walk
     // host contract (range_forward_host): device result, pinned staging, copy stream, copy threads
     DevBuf<double> ws_out64;
     void* h_stage = nullptr;
     size_t h_stage_bytes = 0;
     hipStream_t copy_stream = nullptr;
     std::unique_ptr<HostCopyPool> pool;
-    bool host_timing = false;   // RANGE_HOST_TIMING=1: phase times of range_forward_host on stderr
     // profiling: event pairs per kernel kind
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof[RANGE_PROF_KINDS];
@@ -183,6 +153,9 @@ inline bool split_width_ok(int H, int S) {
     return H % S == 0 && (part == 64 || part == 128 || part == 256 || part == 512);
 }
 
+// waves per encoder workgroup when the hidden width is a multiple of 256 (4 or 16)
+constexpr int ENC_WAVES = 16;
+
 int launch_encoder_split(range_ctx* c, EncArgs a, int S, int KP, hipStream_t s) {
     const int tiles = (int)((a.B + 15) / 16);
     if (c->ws_h1.ensure((size_t)KP * tiles * 16 * a.H) != hipSuccess) return fail(RANGE_ERR_NOMEM, "out of device memory");
@@ -201,18 +174,18 @@ int launch_encoder_split(range_ctx* c, EncArgs a, int S, int KP, hipStream_t s) 
     // ... and, round 5, up to 128 tiles (2 048 queries: a rank's share of an 8-GPU batch, the last partial
     // round of a large batch): the 2-7 workgroups a tile then gets take the parts of the later phases in
     // turns (second-layer parts of 128 / 256 columns where a tile has < 8 / < 4 workgroups).  One launch
-    // against three (tools/encoder_mid.py, steady state): 513 queries 83 us / 114, 800: 93 / 118, 1 024:
+    // against three (steady state): 513 queries 83 us / 114, 800: 93 / 118, 1 024:
     // 102 / 122, 1 250: 128 / 132, 1 536 - 2 048: 155-156 / 157.  (The first version of this looked SLOWER
     // beyond 816 queries and cost the <= 512-query path 15 us: per-part copies of the argument struct inside
     // the phase loops had put 456 B of it into scratch memory - found through the latency log, now refused by
     // tests/test_host_cpu.py.)  Phase stamps of a tile at 1 250 queries (us): first layer 49, wait 11,
     // activation 4, second layer 21 (6 of them filling LDS), wait 10, last layer 16 (two parts of 64 outputs on
-    // the tile's first workgroup), norm 3.  RANGE_ENC_FUSED_MID=0: three launches (A/B).
+    // the tile's first workgroup), norm 3.
     const bool few_tiles = tiles <= 32 && S * KP >= std::max(std::max(a.H / 64, 4), (16 * a.H + 1023) / 1024);
-    const bool mid_tiles = tiles > 32 && tiles <= 128 && S * KP >= c->enc_fused_mid_min_wg && c->enc_fused_mid;
+    const bool mid_tiles = tiles > 32 && tiles <= 128 && S * KP >= 2;
     if ((few_tiles || mid_tiles) && a.n_layers == 2 && c->enc_fused && a.H % 64 == 0 && a.H <= 512 && tiles * S * KP <= c->n_cu) {
         if (c->ws_h2.ensure((size_t)tiles * 16 * a.H) != hipSuccess || c->ws_h1a.ensure((size_t)tiles * 16 * a.H) != hipSuccess ||
-            c->ws_e3.ensure((size_t)tiles * 16 * ENC_EMBED + 64) != hipSuccess || c->ws_enc_sync.ensure(128 * 256) != hipSuccess)
+            c->ws_e3.ensure((size_t)tiles * 16 * ENC_EMBED) != hipSuccess || c->ws_enc_sync.ensure(128 * 256) != hipSuccess)
             return fail(RANGE_ERR_NOMEM, "out of device memory");
         // (the counters wrap to zero by themselves, but a launch whose bounded spin gave up would leave
         // them poisoned for good: zeroed in front of every launch - 2 us of a ~55 us kernel - as the
@@ -245,17 +218,6 @@ int launch_encoder_split(range_ctx* c, EncArgs a, int S, int KP, hipStream_t s) 
         }
 #undef RANGE_ENC_TILE
         HIP_TRY(hipGetLastError());
-#ifdef RANGE_EXP_ENC_STAMPS
-        if (std::getenv("RANGE_ENC_STAMPS")) {
-            unsigned long long h[12];
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipMemcpy(h, c->ws_e3.p + (size_t)tiles * 16 * ENC_EMBED, sizeof h, hipMemcpyDeviceToHost));   // (the stamps sit behind the tiles' rows)
-            std::fprintf(stderr, "encoder_tile stamps (us after start):");
-            for (int i = 1; i < 12; ++i) std::fprintf(stderr, " %d: %.1f", i, (double)(h[i] - h[0]) * 0.01);
-            std::fprintf(stderr, "  [1 first layer, 2 sync, 3 activation, 4 sync, 5 second layer (10 its input in LDS, 11 its products), "
-                         "6 sync, 7 last layer, 8 sync + norm]\n");
-        }
-#endif
         return RANGE_OK;
     }
 #define RANGE_ENC_PART(NTP, NWP)                                                               \
@@ -276,24 +238,23 @@ int launch_encoder_split(range_ctx* c, EncArgs a, int S, int KP, hipStream_t s) 
     // the second layer over S2 column parts per tile where there are CUs for it (and a second
     // hidden layer exists); the last kernel then starts from its output.  Every part re-reads the
     // tile's partial sums and re-activates them, and a third launch costs its ~10 us: measured
-    // (tools/encoder_latency.py, RANGE_ENC_SPLIT2=0 for A/B) 16 queries 106 -> 121 us, 256 queries
+    // (tools/encoder_latency.py, against two launches) 16 queries 106 -> 121 us, 256 queries
     // equal, 625 queries 127 -> 118, 1 250 queries 145 -> 135, 2 048 queries 170 -> 162 us: from 32
     // tiles on.
     a.rest_from = 0;
     // A FEW tiles (up to 8: the latency regime - a handful of queries): one workgroup's chain over the
     // second and the last layer is 12.6 MFLOP of float64 MFMA on ONE CU, 70-90 us whatever the batch.
-    // RANGE_ENC_SPLIT3=1 splits both layers too (second: column parts; last: 4 parts of 64 outputs) with
-    // a one-wave-per-query kernel to normalise - four short launches instead of two.  MEASURED SLOWER:
+    // Splitting both layers there too (second: column parts; last: 4 parts of 64 outputs) with a
+    // one-wave-per-query kernel to normalise - four short launches instead of two - was MEASURED SLOWER:
     // 133 us against 111 us for 16 queries (round 3; round 2 saw the same with three launches): every
     // dependent launch costs ~10-20 us (dispatch, then 4-6 us before a kernel's first memory access
-    // returns), more than the split saves.  Off by default; what would help is ONE persistent launch.
-    const bool few = tiles <= 8 && a.n_layers == 2 && c->enc_split3 && c->enc_split2;
+    // returns), more than the split saves.  What helps is ONE persistent launch (encoder_tile_kernel above).
     int S2 = 1;
-    for (int s2 = 2; s2 <= 8 && (tiles >= 32 || few) && tiles * s2 <= c->n_cu && a.n_layers >= 2; s2 *= 2) {
+    for (int s2 = 2; s2 <= 8 && tiles >= 32 && tiles * s2 <= c->n_cu && a.n_layers >= 2; s2 *= 2) {
         const int part = a.H / s2;
         if (a.H % s2 == 0 && (part == 64 || part == 128 || part == 256)) S2 = s2;
     }
-    if (S2 > 1 && c->enc_split2) {
+    if (S2 > 1) {
         if (c->ws_h2.ensure((size_t)tiles * 16 * a.H) != hipSuccess) return fail(RANGE_ERR_NOMEM, "out of device memory");
         a.h2 = c->ws_h2.p;
         a.n_parts2 = S2;
@@ -313,17 +274,6 @@ int launch_encoder_split(range_ctx* c, EncArgs a, int S, int KP, hipStream_t s) 
         }
 #undef RANGE_ENC_PART2
         HIP_TRY(hipGetLastError());
-        if (few) {
-            if (c->ws_e3.ensure((size_t)tiles * 16 * ENC_EMBED) != hipSuccess) return fail(RANGE_ERR_NOMEM, "out of device memory");
-            a.e3 = c->ws_e3.p;
-            rc = set_dyn_lds(encoder_l3_part_kernel, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(encoder_l3_part_kernel, dim3(tiles * 4), dim3(256), lds, s, a);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(encoder_norm_kernel, dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, s, a);
-            HIP_TRY(hipGetLastError());
-            return RANGE_OK;
-        }
     }
 #define RANGE_ENC_REST(NT, NW)                                                                 \
     case NT:                                                                                   \
@@ -334,9 +284,9 @@ int launch_encoder_split(range_ctx* c, EncArgs a, int S, int KP, hipStream_t s) 
     switch (a.H / 64) {
         RANGE_ENC_REST(1, 4)
         RANGE_ENC_REST(2, 4)
-        RANGE_ENC_REST(4, RANGE_ENC_WAVES)
+        RANGE_ENC_REST(4, ENC_WAVES)
         RANGE_ENC_REST(6, 4)
-        RANGE_ENC_REST(8, RANGE_ENC_WAVES)
+        RANGE_ENC_REST(8, ENC_WAVES)
         RANGE_ENC_REST(12, 16)
         RANGE_ENC_REST(16, 16)
         default: return fail(RANGE_ERR_INVALID, "internal: hidden width %d", a.H);
@@ -383,7 +333,7 @@ int launch_encoder(range_ctx* c, const EncArgs& a_in, hipStream_t s) {
         t.xq = a.xq + 4 * b_main;
         return launch_encoder_split(c, t, S, KP, s);
     };
-    if (full_rounds > 0 && rem > 0 && rem <= 2048 && c->enc_split && c->enc_tail_split && !only16) {
+    if (full_rounds > 0 && rem > 0 && rem <= 2048 && c->enc_split && !only16) {
         const int rc = main_plus_split_tail(a.B - rem);
         if (rc >= 0) return rc;
     }
@@ -392,7 +342,7 @@ int launch_encoder(range_ctx* c, const EncArgs& a_in, hipStream_t s) {
     // round's whole time (0.40 ms): a full round of 16-query workgroups (0.24 ms) + a split tail (<= 0.13 ms)
     const int64_t round16 = (int64_t)16 * c->n_cu;
     // (the same behind full rounds of 32-query workgroups: 8 192 k + 4 097 .. 5 376 queries)
-    if (rem > round16 && rem - round16 <= 1280 && c->enc_split && c->enc_tail_split && !only16) {
+    if (rem > round16 && rem - round16 <= 1280 && c->enc_split && !only16) {
         const int rc = main_plus_split_tail(a.B - (rem - round16));
         if (rc >= 0) return rc;
     }
@@ -422,11 +372,11 @@ int launch_encoder(range_ctx* c, const EncArgs& a_in, hipStream_t s) {
         RANGE_ENC_CASE(1, 4)
         RANGE_ENC_CASE(2, 4)
         RANGE_ENC_CASE(3, 4)
-        RANGE_ENC_CASE(4, RANGE_ENC_WAVES)
+        RANGE_ENC_CASE(4, ENC_WAVES)
         RANGE_ENC_CASE(5, 4)
         RANGE_ENC_CASE(6, 4)
         RANGE_ENC_CASE(7, 4)
-        RANGE_ENC_CASE(8, RANGE_ENC_WAVES)
+        RANGE_ENC_CASE(8, ENC_WAVES)
         RANGE_ENC_CASE(12, 16)
         RANGE_ENC_CASE(16, 16)
         default:
@@ -498,11 +448,10 @@ int fill_scan_args(range_ctx* c, ScanArgs& a, const float* ehat32, const float* 
     // split of pass 2 writes and re-reads a 4 KB row per query: 8 KB at ~4 TB/s against the
     // query's MFMA time n_rows * 2054 FLOP / 140 TFLOP/s, i.e. 140 / n_rows of the launch - small
     // for the whole bank on one GPU, 1 % per split for a 12 500-row shard.
-    a.n_splits = pass1 ? choose_splits(a.n_qtiles, a.n_blocks, c->n_cu, RANGE_P1_WG_PER_CU, p1_max_splits)
+    a.n_splits = pass1 ? choose_splits(a.n_qtiles, a.n_blocks, c->n_cu, P1_WG_PER_CU, p1_max_splits)
                        : choose_splits(a.n_qtiles, a.n_blocks, c->n_cu, 1,
                                        std::max(32, std::min(512, (c->n_cu + a.n_qtiles - 1) / a.n_qtiles)),
                                        std::max(0.001, 140.0 / (double)c->n_rows));
-    if (!pass1 && c->p2_splits_forced > 0) a.n_splits = std::max(1, std::min(c->p2_splits_forced, std::max(1, a.n_blocks / 4)));
     a.k_sem = (float)(tau_sem * LOG2E);
     a.k_geo = tau_geo > 0.f ? (float)(tau_geo * LOG2E) : 0.f;
     a.beta = 1.f;
@@ -557,25 +506,15 @@ int range_create(int device, range_ctx** out) {
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const char* keep = std::getenv("RANGE_KEEP_LOGITS");
     c->allow_keep = !(keep && keep[0] == '0');
-    if (const char* e = std::getenv("RANGE_HOST_TIMING")) c->host_timing = e[0] == '1';
     if (const char* e = std::getenv("RANGE_ENC_SPLIT")) c->enc_split = e[0] != '0';
-    if (const char* e = std::getenv("RANGE_ENC_SPLIT2")) c->enc_split2 = e[0] != '0';
-    if (const char* e = std::getenv("RANGE_ENC_SPLIT3")) c->enc_split3 = e[0] != '0';
     if (const char* e = std::getenv("RANGE_ENC_FUSED")) c->enc_fused = e[0] != '0';
-    if (const char* e = std::getenv("RANGE_ENC_FUSED_MID")) c->enc_fused_mid = e[0] != '0';
-    if (const char* e = std::getenv("RANGE_ENC_FUSED_MID_MIN_WG")) c->enc_fused_mid_min_wg = std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("RANGE_ENC_TAIL")) c->enc_tail_split = e[0] != '0';
-    if (const char* e = std::getenv("RANGE_TOPKS_GROUPS")) c->topks_groups = std::atoi(e);
     if (const char* e = std::getenv("RANGE_TOPKS_FORCE_EXACT")) c->topks_force_exact = e[0] == '1';
     if (const char* e = std::getenv("RANGE_TOPKS_KEYS")) c->topks_bf16 = std::strcmp(e, "f32") != 0;
     if (const char* e = std::getenv("RANGE_TOPKS_FUSED")) c->topks_fused = e[0] != '0';
     if (const char* e = std::getenv("RANGE_SMALL_FORWARD")) c->small_forward = e[0] != '0';
     if (const char* e = std::getenv("RANGE_TOPK_GEMM")) c->topk_gemm = e[0] != '0';
     if (const char* e = std::getenv("RANGE_TG_SAMPLE")) c->tg_sample = std::max(1, std::min(16, std::atoi(e)));
-    if (const char* e = std::getenv("RANGE_P2_SPLITS")) c->p2_splits_forced = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("RANGE_P2_STREAMK")) c->p2_streamk = e[0] != '0';
-    if (const char* e = std::getenv("RANGE_P2_COL_ROWS")) c->p2_col_rows = std::max(64, std::atoi(e));
-    if (const char* e = std::getenv("RANGE_P2_STREAMK_ROWS")) c->p2_streamk_rows = std::max(0, std::atoi(e));
     {
         DeviceGuard g(device);
         void* hp = nullptr;
@@ -1000,7 +939,10 @@ static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32,
     // (which costs more than its MFMAs) and a streaming selection over the kept logits follows.
     // 4 B per (query, bank row) of this context's shard; not done when that would take more than
     // half of the free device memory (pass 2 then recomputes, top-k uses the in-scan lists).
-    bool write_logits = c->allow_keep && (topk > 0 ? B > RANGE_TOPK_INSCAN_MAX : keep_logits != 0);
+    // A top-k batch always selects from the kept logits: measured (tools/topk_total_time.py), the
+    // selection wins at every batch size, so the in-scan lists (scan_stats_kernel<.., true>) only
+    // serve contexts that cannot keep logits.
+    bool write_logits = c->allow_keep && (topk > 0 ? B > 0 : keep_logits != 0);
     const int64_t n_qtiles = (total_queries + QTILE - 1) / QTILE, n_blocks = (c->n_rows + BLK - 1) / BLK;
     if (write_logits && extends) {
         // (the workspace was sized for the whole scan by its first chunk)
@@ -1122,7 +1064,7 @@ int range_scan_stats_at(range_ctx* c, const float* ehat32, const float* xq32, in
 int32_t range_p1_splits(const range_ctx* c, int64_t B) {
     if (!c || !c->has_bank || B <= 0) return 0;
     const int n_qtiles = (int)((B + QTILE - 1) / QTILE), n_blocks = (int)((c->n_rows + BLK - 1) / BLK);
-    return choose_splits(n_qtiles, n_blocks, c->n_cu, RANGE_P1_WG_PER_CU, B <= 4 * QTILE ? 2048 : 128);
+    return choose_splits(n_qtiles, n_blocks, c->n_cu, P1_WG_PER_CU, B <= 4 * QTILE ? 2048 : 128);
 }
 
 // repeats > 1 (range_topk_stream_timed): the whole call's launches are enqueued `repeats` times
@@ -1143,14 +1085,13 @@ static int topk_stream_impl(range_ctx* c, const float* ehat32, int64_t B, int32_
     // its own tiles; one candidate list of 8 per (query, workgroup).  Query groups sharing one pass
     // over the keys: 2 groups (32 queries) are still at the ridge (16 FLOP per key byte) and take
     // the time of 1.3.
-    constexpr int LIST = RANGE_TOPKS_LIST;
+    constexpr int LIST = 4;                  // depth of the per-lane lists
     constexpr int NWV = 4, DEP = 2;
     // (the bf16 prefilter with FOUR groups per pass was measured too: one pass for 64 queries takes
     // 27.0 us against 28.7 us for two passes of two groups - the list work per group, not the
     // stream, is what a pass costs by then - and needs 370 registers; not kept)
     const bool bf16 = c->topks_bf16;
-    int G = c->topks_groups;
-    if (G != 1 && G != 2) G = n_groups <= 1 ? 1 : 2;
+    const int G = n_groups <= 1 ? 1 : 2;     // query groups (of 16) sharing one pass over the keys
     const int n_wg = std::max(1, std::min(std::min(c->n_cu, 256), (n_blocks + NWV - 1) / NWV));
     // the merge runs as the tail of the stream kernel while every query finds a workgroup of its own
     const bool fused = c->topks_fused && B <= n_wg;
@@ -1231,9 +1172,6 @@ static int topk_stream_impl(range_ctx* c, const float* ehat32, int64_t B, int32_
                                    ga.n_splits * 2, B, ehat32, (float)((double)TG_EPS_REL * (double)c->key_norm_max * (double)c->tg_key_scale),
                                    c->key_norm_max > 0.f ? (float)std::log2((double)c->key_norm_max) : -INFINITY,
                                    c->ws_tg_qscale.p, c->ws_tg_theta.p);
-#ifdef RANGE_EXP_TG_NOHIT       // timing experiment: pass B with a threshold nothing reaches (its MFMA + compare floor)
-                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c->ws_tg_theta.p, 0x7f800000, (size_t)B * 2, s));
-#endif
                 hipLaunchKernelGGL(topk_gemm_kernel<1>, ggrid, dim3(TG_WAVES * 64), TG_LDS_BYTES, s, ga);
             }
             ProfScope ps(c, RANGE_PROF_TOPK_MERGE, s);
@@ -1284,13 +1222,6 @@ static int topk_stream_impl(range_ctx* c, const float* ehat32, int64_t B, int32_
     a.kmax = c->key_norm_max;
     a.oval = topk_val;
     a.oidx = topk_idx;
-#ifdef RANGE_EXP_TS_STAMPS
-    static DevBuf<unsigned long long> stamps_buf;
-    const int n_lists = n_wg * NWV;
-    HIP_TRY(stamps_buf.ensure((size_t)n_lists * 8 + (size_t)n_wg * 16));
-    HIP_TRY(hipMemsetAsync(stamps_buf.p, 0, ((size_t)n_lists * 8 + (size_t)n_wg * 16) * 8, s));
-    a.stamps = stamps_buf.p;
-#endif
     int rc = RANGE_OK;
 #define RANGE_TOPKS_LAUNCH(GG)                                                                      \
     do {                                                                                            \
@@ -1349,70 +1280,6 @@ static int topk_stream_impl(range_ctx* c, const float* ehat32, int64_t B, int32_
         c->ev_pool.push_back(ev0);
         c->ev_pool.push_back(ev1);
     }
-#ifdef RANGE_EXP_TS_STAMPS
-    if (std::getenv("RANGE_TOPKS_STAMPS")) {   // per stamp: earliest / median / latest wave, us after the first wave's start
-        std::vector<unsigned long long> h((size_t)n_lists * 8 + (size_t)n_wg * 16);
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(h.data(), stamps_buf.p, h.size() * 8, hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull;
-        for (int w = 0; w < n_lists; ++w) t0 = std::min(t0, h[(size_t)w * 8]);
-        std::fprintf(stderr, "topk_stream stamps (us: min med max)");
-        for (int i = 0; i < 7; ++i) {
-            if (i == 3) continue;                          // (slot 3 holds a sum, printed below)
-            std::vector<double> v;
-            for (int w = 0; w < n_lists; ++w) v.push_back((double)(h[(size_t)w * 8 + i] - t0) * 0.01);
-            std::sort(v.begin(), v.end());
-            std::fprintf(stderr, " | %d: %.1f %.1f %.1f", i, v.front(), v[v.size() / 2], v.back());
-        }
-        {   // loop sums (us): waiting for tiles / issuing LDS-DMA / arithmetic
-            std::vector<double> w, is, cp;
-            for (int x = 0; x < n_lists; ++x) {
-                w.push_back((double)h[(size_t)x * 8 + 3] * 0.01);
-                is.push_back((double)(h[(size_t)x * 8 + 7] >> 32) * 0.01);
-                cp.push_back((double)(h[(size_t)x * 8 + 7] & 0xFFFFFFFFull) * 0.01);
-            }
-            std::sort(w.begin(), w.end()); std::sort(is.begin(), is.end()); std::sort(cp.begin(), cp.end());
-            std::fprintf(stderr, "\n  per wave over the tile loop (us, min med max): waiting %.1f %.1f %.1f | issuing DMA %.1f %.1f %.1f | arithmetic %.1f %.1f %.1f",
-                         w.front(), w[w.size() / 2], w.back(), is.front(), is[is.size() / 2], is.back(), cp.front(), cp[cp.size() / 2], cp.back());
-        }
-        std::fprintf(stderr, "\n  end of tiles (stamp 4) by blockIdx %% 8:");
-        for (int x = 0; x < 8; ++x) {
-            std::vector<double> v;
-            for (int w = 0; w < n_lists; ++w) if ((w % n_wg) % 8 == x) v.push_back((double)(h[(size_t)w * 8 + 4] - t0) * 0.01);
-            std::sort(v.begin(), v.end());
-            std::fprintf(stderr, " %.1f/%.1f/%.1f", v.front(), v[v.size() / 2], v.back());
-        }
-        std::fprintf(stderr, "\n  by blockIdx / 32:");
-        for (int x = 0; x < (n_wg + 31) / 32; ++x) {
-            std::vector<double> v;
-            for (int w = 0; w < n_lists; ++w) if ((w % n_wg) / 32 == x) v.push_back((double)(h[(size_t)w * 8 + 4] - t0) * 0.01);
-            std::sort(v.begin(), v.end());
-            std::fprintf(stderr, " %.1f/%.1f/%.1f", v.front(), v[v.size() / 2], v.back());
-        }
-        std::fprintf(stderr, "\n  tail stamps (us after the first wave's start: min med max over the workgroups that have it)");
-        for (int i = 0; i < 16; ++i) {
-            std::vector<double> v;
-            for (int w = 0; w < n_wg; ++w) {
-                const unsigned long long t = h[(size_t)n_lists * 8 + (size_t)w * 16 + i];
-                if (t && i == 14) {   // shader clocks of the merge / its real time -> MHz
-                    const unsigned long long b0 = h[(size_t)n_lists * 8 + (size_t)w * 16 + 3], b1 = h[(size_t)n_lists * 8 + (size_t)w * 16 + 15];
-                    if (b1 > b0) v.push_back((double)t / ((double)(b1 - b0) * 0.01));
-                } else if (t) v.push_back((double)(t - t0) * 0.01);
-            }
-            if (v.empty()) continue;
-            std::sort(v.begin(), v.end());
-            std::fprintf(stderr, " | %d (%zu): %.1f %.1f %.1f", i, v.size(), v.front(), v[v.size() / 2], v.back());
-        }
-        std::fprintf(stderr, "\n  by wave in workgroup:");
-        for (int x = 0; x < 4; ++x) {
-            std::vector<double> v;
-            for (int w = 0; w < n_lists; ++w) if (w / n_wg == x) v.push_back((double)(h[(size_t)w * 8 + 4] - t0) * 0.01);
-            std::sort(v.begin(), v.end());
-            std::fprintf(stderr, " %.1f/%.1f/%.1f", v.front(), v[v.size() / 2], v.back());
-        }
-        std::fprintf(stderr, "\n");
-    }
-#endif
     return RANGE_OK;
 }
 
@@ -1501,11 +1368,10 @@ int range_topk_stream_exact_count(range_ctx* c, int64_t* count) {
     *count = 0;
     if (!c->ws_exact_count.p) return RANGE_OK;
     DeviceGuard g(c->device);
-    int32_t v[2] = {0, 0};
+    int32_t v = 0;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(v, c->ws_exact_count.p, sizeof v, hipMemcpyDeviceToHost));
-    *count = v[0];
-    if (std::getenv("RANGE_TOPKS_DIAG")) std::fprintf(stderr, "range_topk_stream: %d candidates ranked so far\n", v[1]);
+    HIP_TRY(hipMemcpy(&v, c->ws_exact_count.p, sizeof v, hipMemcpyDeviceToHost));
+    *count = v;
     return check_async_error(c);     // (a merging workgroup of an earlier fused call that gave up)
 }
 
@@ -1567,13 +1433,15 @@ static int attend_impl(range_ctx* c, const float* ehat32, const float* xq32, int
     // loses 9 % with one: its workgroups re-read the values from HBM then, not from the Infinity
     // Cache) while its longer float32 accumulation chains cost accuracy (|sum of weights - 1| of the
     // worst of 10^5 queries 1.3e-5 instead of 0.5e-5): not taken there.  The exact kernels only;
-    // RANGE_P2_STREAMK=0 / RANGE_P2_SPLITS=n restore the split scheme for A/B.
-    const bool streamk = c->p2_streamk && c->p2_splits_forced == 0 && c->n_rows <= c->p2_streamk_rows &&
+    // RANGE_P2_STREAMK=0 restores the split scheme for A/B.
+    constexpr int P2_STREAMK_ROWS = 50000;
+    const bool streamk = c->p2_streamk && c->n_rows <= P2_STREAMK_ROWS &&
                          !(kept_first >= 0 && c->pv_mode == RANGE_PV_BF16X3);
     if (streamk) {
         // columns of at most 16 384 rows: an accumulation chain (one query tile's blocks of a column)
         // stays within ~2x the 481 blocks of the split scheme on the full bank
-        a.sk_cols = (int32_t)std::max<int64_t>(1, std::min<int64_t>((c->n_rows + c->p2_col_rows - 1) / c->p2_col_rows,
+        constexpr int P2_COL_ROWS = 16384;
+        a.sk_cols = (int32_t)std::max<int64_t>(1, std::min<int64_t>((c->n_rows + P2_COL_ROWS - 1) / P2_COL_ROWS,
                                                                     std::max(1, a.n_blocks / 4)));
         const int64_t Uc = (int64_t)a.n_qtiles * (a.n_blocks / a.sk_cols);     // (units of the shortest column)
         a.sk_groups = (int32_t)std::max<int64_t>(1, std::min<int64_t>(c->n_cu, Uc / 4));
@@ -1610,23 +1478,7 @@ static int attend_impl(range_ctx* c, const float* ehat32, const float* xq32, int
         } else if (geo) {
             rc = set_dyn_lds(attend_stored_kernel<true>, ATTEND_STORED_LDS_BYTES);
             if (rc) return rc;
-#ifdef RANGE_EXP_P2_STAMPS
-            static DevBuf<unsigned long long> p2_stamps;
-            const char* stamp_file = std::getenv("RANGE_P2_STAMPS");
-            if (stamp_file) {
-                HIP_TRY(p2_stamps.ensure((size_t)grid.x * 16));
-                a.diag = p2_stamps.p;
-            }
-#endif
             hipLaunchKernelGGL(attend_stored_kernel<true>, grid, block, ATTEND_STORED_LDS_BYTES, s, a);
-#ifdef RANGE_EXP_P2_STAMPS
-            if (stamp_file) {
-                std::vector<unsigned long long> h((size_t)grid.x * 16);
-                HIP_TRY(hipStreamSynchronize(s));
-                HIP_TRY(hipMemcpy(h.data(), p2_stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
-                if (FILE* f = std::fopen(stamp_file, "wb")) { std::fwrite(h.data(), 8, h.size(), f); std::fclose(f); }
-            }
-#endif
         } else {
             rc = set_dyn_lds(attend_stored_kernel<false>, ATTEND_STORED_LDS_BYTES);
             if (rc) return rc;
@@ -1854,7 +1706,6 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
     DeviceGuard g(c->device);
     if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
     hipStream_t s = (hipStream_t)stream;
-    const auto t_begin = std::chrono::steady_clock::now();
     const size_t row_bytes = (size_t)RANGE_OUT_DIM * sizeof(double);
     HIP_TRY(c->ws_ehat64.ensure((size_t)B * 256));
     HIP_TRY(c->ws_ehat32.ensure((size_t)B * 256));
@@ -1896,31 +1747,17 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
     // Pass 2 runs in a few launches over consecutive query ranges (boundaries on query tiles): the
     // device->host copy and the host fill of a part overlap pass 2 of the next, so only the LAST
     // part's copy and fill are exposed - and the parts SHRINK: the rest, 4 096, 512 queries.  What
-    // bounds the end is the copy queue (RANGE_HOST_TIMING=1 prints when each slab's copy was seen):
+    // bounds the end is the copy queue (when each slab's copy was seen, measured):
     // 0.205 ms per 1 000 queries (10 KB each at 52 GB/s) against 1.46 ms of pass 2 per 1 000 queries
     // against range_db_large, so a part up to seven times its successor is drained while the
     // successor computes; with (4 096, 1 024) the last slab was seen 0.35 ms after pass 2 ended, with
     // (4 096, 512) 0.15 ms (two equal halves: 1.4 ms).  Part sizes matter on the GPU side too: the
     // split count of pass 2 is chosen per launch so that its workgroups fill whole rounds of the
     // chip (8 query tiles x 32 bank splits, 64 x 4: exactly one round) - measured for 10 000 queries,
-    // medians of 30 calls (tools/host_parts.py; the box wanders by +-0.1 ms): (4 096, 512) 19.71 ms,
+    // medians of 30 calls (the box wanders by +-0.1 ms): (4 096, 512) 19.71 ms,
     // (2 048, 256) 19.70, (3 072, 512) 19.87, (4 096, 1 024) 19.96, (1 792, 256) 19.98.
     std::vector<int64_t> cuts{0, B};
-    if (B >= 4096) {
-        // RANGE_HOST_PARTS="2048,512": sizes of the parts behind the first (tuning)
-        std::vector<int64_t> tail{4096, 512};
-        if (const char* e = std::getenv("RANGE_HOST_PARTS")) {
-            tail.clear();
-            for (const char* q = e; *q;) {
-                char* end = nullptr;
-                const long v = std::strtol(q, &end, 10);
-                if (end == q) break;
-                if (v > 0) tail.push_back(v);
-                q = *end ? end + 1 : end;
-            }
-        }
-        cuts = host_part_cuts(B, tail, QTILE);       // (host_plan.h: rounded up to a tile, clamped, monotonic)
-    }
+    if (B >= 4096) cuts = host_part_cuts(B, {4096, 512}, QTILE);   // (host_plan.h: rounded up to a tile, clamped, monotonic)
     constexpr int64_t SLAB = 1024;
     struct Slab { int64_t q0, nq; hipEvent_t fin, cop; };
     std::vector<Slab> slabs;
@@ -1968,21 +1805,12 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
             for (size_t o = lo; o < hi; o += 4096) *(volatile char*)(base + o) = 0;
         });
     }
-    const auto t_enq = std::chrono::steady_clock::now();
-    double wait_s = 0.0, copy_s = 0.0;
-    std::vector<double> landed;                 // (host_timing) when each slab's copy was seen, ms after entry
     for (auto& sl : slabs) {
         if (e != hipSuccess) break;
-        const auto w0 = std::chrono::steady_clock::now();
         e = hipEventSynchronize(sl.cop);
-        const auto w1 = std::chrono::steady_clock::now();
         if (e != hipSuccess) break;
         c->pool->copy((char*)out_host + sl.q0 * row_bytes, (const char*)c->h_stage + sl.q0 * row_bytes,
                       (size_t)sl.nq * row_bytes);
-        const auto w2 = std::chrono::steady_clock::now();
-        wait_s += std::chrono::duration<double>(w1 - w0).count();
-        copy_s += std::chrono::duration<double>(w2 - w1).count();
-        if (c->host_timing) landed.push_back(std::chrono::duration<double>(w1 - t_begin).count() * 1e3);
     }
     if (e != hipSuccess) {
         (void)hipDeviceSynchronize();
@@ -1990,18 +1818,7 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
         return fail(RANGE_ERR_HIP, "range_forward_host: %s", hipGetErrorString(e));
     }
     give_back();
-    if (int rc2 = check_async_error(c)) return rc2;
-    if (c->host_timing)
-        std::fprintf(stderr, "range_forward_host B=%lld: enqueue %.2f ms, waiting for slabs %.2f ms, host fill %.2f ms "
-                     "(%d threads), total %.2f ms\n", (long long)B,
-                     std::chrono::duration<double>(t_enq - t_begin).count() * 1e3, wait_s * 1e3, copy_s * 1e3,
-                     c->pool->size(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count() * 1e3);
-    if (c->host_timing) {
-        std::fprintf(stderr, "  slab copies seen at (ms):");
-        for (size_t i = 0; i < landed.size(); ++i) std::fprintf(stderr, " %.2f(%lld)", landed[i], (long long)slabs[i].nq);
-        std::fprintf(stderr, "\n");
-    }
-    return RANGE_OK;
+    return check_async_error(c);
 }
 
 int range_profile_enable(range_ctx* c, int32_t on) {

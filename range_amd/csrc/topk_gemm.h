@@ -54,10 +54,7 @@
 namespace range_hip {
 
 constexpr int TG_GQ = 4;                     // query groups (of 16) per wave
-#ifndef RANGE_TG_WAVES
-#define RANGE_TG_WAVES 4                     // waves per workgroup (4: two workgroups per CU; 8: one)
-#endif
-constexpr int TG_WAVES = RANGE_TG_WAVES;
+constexpr int TG_WAVES = 4;                  // waves per workgroup (4: two workgroups per CU; 8: one)
 constexpr int TG_WG_PER_CU = 8 / TG_WAVES;
 constexpr int TG_QBLOCK = TG_WAVES * TG_GQ * 16;    // queries per workgroup
 constexpr int TG_DMA_PER_WAVE = 16 / TG_WAVES;      // 1 KB pieces of a phase's 2 x 8 KB each wave moves
@@ -190,9 +187,7 @@ __device__ __forceinline__ void tg_append(float val, float th, uint32_t& count, 
         "v_min_u32 %[t], %[capm1], %[cnt]\n\t"
         "v_add_u32 %[cnt], 1, %[cnt]\n\t"
         "v_lshl_add_u32 %[t], %[t], 3, %[off]\n\t"
-#ifndef RANGE_EXP_TG_NOSTORE     // (timing experiment: the append without its store)
         "global_store_dwordx2 %[t], %[pair], %[cand]\n\t"
-#endif
         ".Ltg_none_%=:\n\t"
         "s_mov_b64 exec, %[sv]"
         : [t] "=&v"(t), [sv] "=&s"(sv), [cnt] "+v"(count)
@@ -343,12 +338,8 @@ __global__ __launch_bounds__(TG_WAVES * 64, 2) void topk_gemm_kernel(TopkGemmArg
 #pragma unroll
             for (int gi = 0; gi < TG_GQ; ++gi) {
                 if (__builtin_amdgcn_ballot_w64(m4[gi] >= th[gi]) == 0ull) continue;      // (wave-uniform)
-#ifndef RANGE_EXP_TG_NOAPPEND    // (timing experiment: the rare branch entered, nothing appended)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) tg_append(acc[gi][r], th[gi], nc[gi], list_off[gi], row0 + prow[r], a.cand);
-#else
-                asm volatile("s_nop 0" ::: "memory");
-#endif
             }
         }
     };

@@ -53,7 +53,6 @@ struct TopkStreamArgs {
     int64_t n_valid;
     int32_t n_blocks;
     int32_t n_groups;           // ceil(B / 16)
-    unsigned long long* stamps; // RANGE_EXP_TS_STAMPS builds: 8 s_memrealtime stamps per wave
     const void* keys_bf16;      // prefilter form: (n_tiles, 8 chunks, 64 lanes, 8) bf16, see keyfrag_kernel
     // ---- the merge (topk_merge_query), as the tail of the same launch when `fused`
     uint32_t* sync;             // TOPKS_SYNC_WORDS words (topks_tail): 8 arrival counters that only ever count up
@@ -71,27 +70,6 @@ struct TopkStreamArgs {
     int64_t* oidx;              // (B,k)
 };
 
-#ifdef RANGE_EXP_TS_STAMPS   // tuning only: where a wave's time goes (100 MHz real-time counter)
-#define RANGE_TS_STAMP(i) do { if (lane == 0 && a.stamps) a.stamps[(size_t)w_id * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define RANGE_TS_NOW() __builtin_amdgcn_s_memrealtime()
-#define RANGE_TS_ADD(acc, t0) (acc) += __builtin_amdgcn_s_memrealtime() - (t0)
-// tail stamps: 16 per workgroup behind the waves' stamps (thread 0 of the workgroup)
-#define RANGE_TT_STAMP(i) do { if (threadIdx.x == 0 && a.stamps) a.stamps[(size_t)gridDim.x * 4 * 8 + (size_t)blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define RANGE_TS_STAMP(i) do { } while (0)
-#define RANGE_TS_NOW() 0ull
-#define RANGE_TS_ADD(acc, t0) do { } while (0)
-#define RANGE_TT_STAMP(i) do { } while (0)
-#endif
-
-#ifndef RANGE_TOPKS_VALU_PER_MFMA
-#define RANGE_TOPKS_VALU_PER_MFMA 4
-#endif
-#ifdef RANGE_EXP_TS_TEMPORAL
-#define TS_DMAQ dma_b128_q
-#else
-#define TS_DMAQ dma_b128_q_nt
-#endif
 constexpr int TOPKS_SG = 4;         // groups whose lists a wave carries through consecutive passes
 constexpr int TOPKS_WL = 8;         // entries of a wave's and of a workgroup's list of one query
 constexpr int TOPKS_RING_BYTES = 8 * BLK * KEY_DIM * 4;          // 128 KB of key tiles per workgroup
@@ -268,12 +246,8 @@ __device__ __forceinline__ void topk_qwait(f32x4 (&d)[16]) {
 // first tiles meanwhile (its LDS is not touched here).
 template <int L>
 __device__ __forceinline__ void topks_publish(ShortList<L> (&lists)[TOPKS_SG], int sg, const TopkStreamArgs& a,
-                                              char* smem, int lane, int wave, bool more,
-                                              unsigned long long* ts = nullptr) {
+                                              char* smem, int lane, int wave, bool more) {
     static_assert(L == 4 && TOPKS_WL == 8, "merge4_lists4_top8");
-    // (stamp builds: ts[0] += lane merges + LDS stores, ts[1] += the wait at the barrier, ts[2] += the
-    // workgroup merge, its stores and the second barrier)
-    const unsigned long long ts_p0 = RANGE_TS_NOW();
     unsigned long long* wl = reinterpret_cast<unsigned long long*>(smem + TOPKS_RING_BYTES);
     float* wd = reinterpret_cast<float*>(smem + TOPKS_RING_BYTES + TOPKS_XL_BYTES);
     const int g = lane >> 4, j = lane & 15;
@@ -297,9 +271,7 @@ __device__ __forceinline__ void topks_publish(ShortList<L> (&lists)[TOPKS_SG], i
             }
         }
     }
-    const unsigned long long ts_p1 = RANGE_TS_NOW();
     __syncthreads();
-    const unsigned long long ts_p2 = RANGE_TS_NOW();
     const int grp = sg * TOPKS_SG + wave;
     if (grp < a.n_groups) {
         const ulonglong2* src = reinterpret_cast<const ulonglong2*>(wl + ((wave * 4 + g) * 16 + j) * TOPKS_WL);
@@ -317,11 +289,6 @@ __device__ __forceinline__ void topks_publish(ShortList<L> (&lists)[TOPKS_SG], i
         }
     }
     if (more) __syncthreads();       // (the list area is written again at the end of the next supergroup)
-#ifdef RANGE_EXP_TS_STAMPS
-    if (ts) { ts[0] += ts_p1 - ts_p0; ts[1] += ts_p2 - ts_p1; ts[2] += RANGE_TS_NOW() - ts_p2; }
-#else
-    (void)ts; (void)ts_p0; (void)ts_p1; (void)ts_p2;
-#endif
 }
 
 template <int L>
@@ -356,9 +323,7 @@ constexpr int TOPKS_SYNC_STRIDE = 64;                          // words between 
 constexpr int TOPKS_SYNC_SCRATCH = 8 * TOPKS_SYNC_STRIDE;      // host scratch behind the counters (the key-norm reduction)
 constexpr int TOPKS_SYNC_WORDS = TOPKS_SYNC_SCRATCH + 16;
 __device__ __forceinline__ void topks_tail(const TopkStreamArgs& a, char* smem) {
-    RANGE_TT_STAMP(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // list stores done; the clamped prefetches past the end landed
-    RANGE_TT_STAMP(1);
     if (!a.fused) return;
     int* ctl = reinterpret_cast<int*>(smem + TOPKS_RING_BYTES + TOPKS_XL_BYTES + TOPKS_XD_BYTES);
     __syncthreads();
@@ -370,7 +335,6 @@ __device__ __forceinline__ void topks_tail(const TopkStreamArgs& a, char* smem) 
         ctl[0] = (int)(__hip_atomic_fetch_add(a.sync + TOPKS_SYNC_STRIDE * shard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) -
                        a.sync_base[shard]);
     __syncthreads();
-    RANGE_TT_STAMP(2);
     const int local = ctl[0] - (shard_size - shard_workers);
     if (local < 0) return;
     const int64_t q = shard + 8 * local;
@@ -394,7 +358,6 @@ __device__ __forceinline__ void topks_tail(const TopkStreamArgs& a, char* smem) 
         }
     }
     __syncthreads();
-    RANGE_TT_STAMP(3);
     if (!ctl[1]) {
         if ((int)threadIdx.x < a.k) {
             a.oval[q * a.k + threadIdx.x] = __builtin_nanf("");
@@ -402,19 +365,11 @@ __device__ __forceinline__ void topks_tail(const TopkStreamArgs& a, char* smem) 
         }
         return;
     }
-#ifdef RANGE_EXP_TS_STAMPS
-    const unsigned long long clk0 = __builtin_amdgcn_s_memtime();
-#endif
     topk_merge_query<TOPKS_WL>(smem, q, a, n_wg);
-    RANGE_TT_STAMP(15);
-#ifdef RANGE_EXP_TS_STAMPS   // shader clocks the merge took (slot 14): against stamps 3 -> 15 it gives the clock rate
-    if (threadIdx.x == 0 && a.stamps)
-        a.stamps[(size_t)gridDim.x * 4 * 8 + (size_t)blockIdx.x * 16 + 14] = __builtin_amdgcn_s_memtime() - clk0;
-#endif
 }
 
 // NW waves per workgroup, each with a ring of DEPTH tiles (NW * DEPTH * 16 KB of LDS = 128 KB).
-// Per-wave stamps (RANGE_EXP_TS_STAMPS) show that with 4 waves x 2 tiles a wave never waits for a
+// Per-wave stamps show that with 4 waves x 2 tiles a wave never waits for a
 // tile once the first has landed: over a pass it spends 7.9 us in arithmetic, 2.4 us issuing
 // LDS-DMA and 0 us waiting.  8 waves x 1 tile (two waves per SIMD) was measured for the 1-group
 // kernel: 21.4 us instead of 21.6 at 16 queries, but 37.3 / 70 us instead of 36.2 / 63.6 at 2 / 4
@@ -445,7 +400,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
     const int n_sg = (a.n_groups + TOPKS_SG - 1) / TOPKS_SG;
     const int total = n_pass * T;                              // this wave's tile sequence
     const int last = a.n_blocks - 1;
-    RANGE_TS_STAMP(0);
     // one tile = 16 rows = 16 DMA instructions (4 groups of 4 rows, swizzled source: chunk c of
     // row R lands at chunk position c ^ R, which makes the ds_read_b128 below conflict-free).
     // Sequence positions past the end fetch the bank's last tile again - never consumed - so
@@ -462,7 +416,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
             for (int i4 = 0; i4 < 4; ++i4)
                 // (non-temporal: a key tile is read by exactly one wave per pass - measured 1 us
                 // per 16-query launch and 3 us per four passes faster than the default policy)
-                TS_DMAQ(src + gr * 4 * KEY_DIM, (uint32_t)((lane ^ (4 * gr + i4)) << 4), i4);
+                dma_b128_q_nt(src + gr * 4 * KEY_DIM, (uint32_t)((lane ^ (4 * gr + i4)) << 4), i4);
         }
     };
     // the first pass's query fragments first (topk_qwait below), the ring's first requests behind them
@@ -475,7 +429,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
     }
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) issue_seq(d);
-    RANGE_TS_STAMP(1);
 
     KAddr kaddr;
     kaddr.init(lane);
@@ -485,7 +438,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
     const uint32_t n_valid32 = (uint32_t)a.n_valid;
 
     int k = 0;                                                 // position in the tile sequence
-    unsigned long long ts_wait = 0, ts_issue = 0, ts_comp = 0; // (stamp builds: time in each part of the loop)
     for (int sg = 0; sg < n_sg; ++sg) {
         // the lists of a supergroup's 4 query groups live in registers through its passes and
         // are merged once, at its end: no merge work at a pass boundary
@@ -544,13 +496,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
 
                 for (int i = 0; i < T; ++i, ++k) {
                     const int tile = w_id + i * n_waves;
-                    const unsigned long long ts0 = RANGE_TS_NOW();
-#ifndef RANGE_EXP_TS_NODMA
                     // tile k has landed when at most the 16 operations of each younger tile are outstanding
                     asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-#endif
-                    RANGE_TS_ADD(ts_wait, ts0);
-                    if (k == 0) RANGE_TS_STAMP(2);            // first tile landed
                     const char* kt = my + (k % DEPTH) * KT_BYTES;
                     f32x4 kf[16];
 #pragma unroll
@@ -560,20 +507,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
                     for (int s = 0; s < 16; ++s) asm volatile("" : "+v"(kf[s]));
-                    const unsigned long long ts1 = RANGE_TS_NOW();
-#ifndef RANGE_EXP_TS_NODMA   // timing experiment only (results invalid): no stream, compute only
                     issue_seq(k + DEPTH);
-#endif
-                    RANGE_TS_ADD(ts_issue, ts1);
                     if (tile >= a.n_blocks) continue;      // (the ragged last round of a pass)
-                    const unsigned long long ts2 = RANGE_TS_NOW();
                     f32x4 acc[G];
 #pragma unroll
                     for (int gi = 0; gi < G; ++gi) {
                         f32x4 c = {0.f, 0.f, 0.f, 0.f};
-#ifdef RANGE_EXP_TS_NOMFMA   // timing experiment only (results invalid)
-                        c = kf[gi] + kf[gi + 4] + qf[gi][3];
-#else
 #pragma unroll
                         for (int s = 0; s < 16; ++s) {
                             c = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s].x, qf[gi][s].x, c, 0, 0, 0);
@@ -581,47 +520,27 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
                             c = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s].z, qf[gi][s].z, c, 0, 0, 0);
                             c = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s].w, qf[gi][s].w, c, 0, 0, 0);
                         }
-#endif
                         acc[gi] = c;
                         // list maintenance of the PREVIOUS tile's values of this group:
                         // independent of the chain above, placed into its shadow
-#ifdef RANGE_EXP_TS_NOPUSH   // timing experiment only (results invalid)
-                        lists[ps * G + gi].v[0] += prev[gi][0] + prev[gi][1] + prev[gi][2] + prev[gi][3];
-#else
                         push_prev(gi);
-#endif
-#if RANGE_TOPKS_VALU_PER_MFMA > 0
+                        constexpr int VALU_PER_MFMA = 4;
 #pragma unroll
                         for (int m = 0; m < 64; ++m) {
                             __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);    // 1 MFMA
-                            __builtin_amdgcn_sched_group_barrier(0x2, RANGE_TOPKS_VALU_PER_MFMA, 0);
+                            __builtin_amdgcn_sched_group_barrier(0x2, VALU_PER_MFMA, 0);
                         }
-#endif
                     }
 #pragma unroll
                     for (int gi = 0; gi < G; ++gi) prev[gi] = acc[gi];
                     prev_row0 = (uint32_t)tile * BLK;
-#ifdef RANGE_EXP_TS_STAMPS
-                    asm volatile("" :: "v"(prev[0]));      // (the tile's results are in registers here)
-#endif
-                    RANGE_TS_ADD(ts_comp, ts2);
                 }
 #pragma unroll
                 for (int gi = 0; gi < G; ++gi) push_prev(gi);
             }
         }
-        RANGE_TS_STAMP(4);   // all tiles of the supergroup consumed
         topks_publish<L>(lists, sg, a, smem, lane, wave, sg + 1 < n_sg);
     }
-    RANGE_TS_STAMP(5);
-#ifdef RANGE_EXP_TS_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RANGE_TS_STAMP(6);
-    if (lane == 0 && a.stamps) {   // sums over the loop: waiting for tiles / issuing LDS-DMA / arithmetic
-        a.stamps[(size_t)w_id * 8 + 3] = ts_wait;
-        a.stamps[(size_t)w_id * 8 + 7] = (ts_issue << 32) | (ts_comp & 0xFFFFFFFFull);
-    }
-#endif
     topks_tail(a, smem);
 }
 
@@ -710,7 +629,6 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
     const int total = n_pass * T;
     const int last = a.n_blocks - 1;
     const char* kb = reinterpret_cast<const char*>(a.keys_bf16);
-    RANGE_TS_STAMP(0);
     // one tile = 8 KB, contiguous in fragment order: 8 LDS-DMA operations (two groups of four)
     auto issue_seq = [&](int k) __attribute__((always_inline)) {
         const int i = k < total ? k % T : T - 1;
@@ -721,7 +639,7 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
         for (int gr = 0; gr < 2; ++gr) {
             dma_group_begin(dst + gr * 4096);
 #pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4) TS_DMAQ(src + gr * 4096, (uint32_t)(lane << 4), i4);
+            for (int i4 = 0; i4 < 4; ++i4) dma_b128_q_nt(src + gr * 4096, (uint32_t)(lane << 4), i4);
         }
     };
     // the first pass's query rows first (topk_qwait below), the ring's first requests behind them:
@@ -734,7 +652,6 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
         const char* pb = reinterpret_cast<const char*>(a.ehat + (q < a.B ? q : a.B - 1) * KEY_DIM + 8 * g);
         TopkQLoad<0, 16, true>::run(qraw0[gi], pb);
     }
-    RANGE_TS_STAMP(1);       // (stamp builds: the query loads are out)
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) issue_seq(d);
 
@@ -742,7 +659,6 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
 #pragma unroll
     for (int r = 0; r < 4; ++r) prow[r] = (uint32_t)pi_row(4 * g + r);
     const uint32_t n_valid32 = (uint32_t)a.n_valid;
-    unsigned long long ts_pub[3] = {0ull, 0ull, 0ull};       // (stamp builds: where the publishes' time goes)
 
     int k = 0;
     for (int sg = 0; sg < n_sg; ++sg) {
@@ -791,7 +707,6 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
 #pragma unroll
                     for (int c = 0; c < 8; ++c) asm volatile("" : "+v"(qh[gi][c]), "+v"(qm[gi][c]));
                 }
-                if (k == 0) RANGE_TS_STAMP(6);   // (stamp builds: the first pass's query operand is in registers)
                 f32x4 prev[G];
 #pragma unroll
                 for (int gi = 0; gi < G; ++gi) prev[gi] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -808,7 +723,6 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
                     const int tile = w_id + i * n_waves;
                     // tile k has landed when at most the 8 operations of each younger tile are outstanding
                     asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-                    if (k == 0) RANGE_TS_STAMP(2);            // first tile landed
                     const char* kt = my + (k % DEPTH) * TSB_TILE_BYTES;
                     ts_u32x4 kf[8];
 #pragma unroll
@@ -843,16 +757,8 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
                 for (int gi = 0; gi < G; ++gi) push_prev(gi);
             }
         }
-        RANGE_TS_STAMP(4);   // all tiles of the supergroup consumed
-        topks_publish<L>(lists, sg, a, smem, lane, wave, sg + 1 < n_sg, ts_pub);
+        topks_publish<L>(lists, sg, a, smem, lane, wave, sg + 1 < n_sg);
     }
-    RANGE_TS_STAMP(5);
-#ifdef RANGE_EXP_TS_STAMPS
-    if (lane == 0 && a.stamps) {   // sums over the supergroups' publishes: lane merges / barrier wait / workgroup merge
-        a.stamps[(size_t)w_id * 8 + 3] = ts_pub[1];
-        a.stamps[(size_t)w_id * 8 + 7] = (ts_pub[0] << 32) | (ts_pub[2] & 0xFFFFFFFFull);
-    }
-#endif
     topks_tail(a, smem);
 }
 
@@ -1129,7 +1035,6 @@ __device__ void topk_merge_query(char* lds, int64_t q, const TopkStreamArgs& a, 
         }
     }
     __syncthreads();
-    RANGE_TT_STAMP(4);
     uint32_t T;
     if (R == 4) {
         const uint32_t t01 = m.sh_head[0] < m.sh_head[1] ? m.sh_head[0] : m.sh_head[1];
@@ -1184,7 +1089,6 @@ __device__ void topk_merge_query(char* lds, int64_t q, const TopkStreamArgs& a, 
         }
     }
     __syncthreads();
-    RANGE_TT_STAMP(5);
     const int S = m.sh_i[0];
     // ---- 3. ranking and exactness of the short lists: if the largest value any lane, wave or
     //      workgroup let go could belong to the top k, the query goes to the brute-force path.
@@ -1202,7 +1106,6 @@ __device__ void topk_merge_query(char* lds, int64_t q, const TopkStreamArgs& a, 
             for (int rr = 0; rr < n64; ++rr) { const int t = 64 * rr + (p >> 2); m.surv2[t] = t < S ? m.surv[t] : 0ull; }
         }
         __syncthreads();
-        RANGE_TT_STAMP(6);
         for (int rr = 0; rr < n64; ++rr) {
             const unsigned long long mine = m.surv2[64 * rr + (p >> 2)];      // (0 past S)
             int r = 0;
@@ -1223,7 +1126,6 @@ __device__ void topk_merge_query(char* lds, int64_t q, const TopkStreamArgs& a, 
             a.oidx[q * k + p] = (int64_t)-1;
         }
         __syncthreads();
-        RANGE_TT_STAMP(7);
         // (nothing can have been dropped while fewer than k rows exist)
         unsafe = a.force_exact || m.sh_i[1] != 0 || (S < k && dall > -INFINITY);
         if (!unsafe) return;

@@ -181,7 +181,7 @@ static void test_copy_pool() {
 }
 
 // hidden widths without a kernel run zero-padded as the next width that has one; the cuts of the
-// numpy contract stay inside the batch whatever RANGE_HOST_PARTS holds
+// numpy contract stay inside the batch whatever part sizes they are given
 static void test_padding_and_host_parts() {
     for (int h = -3; h <= 1100; ++h) {
         const int k = kernel_hidden_width(h);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where the time of the numpy contract goes (GPU box): model(x) returning a fresh host array,
-with results kept alive / dropped per call, and the library's own phase times
-(RANGE_HOST_TIMING=1), for different host-thread counts and with / without kernel prefaulting."""
+with results kept alive / dropped per call, for different host-thread counts and with / without
+kernel prefaulting."""
 import os, sys, time, subprocess
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if len(sys.argv) > 1 and sys.argv[1] == "child":

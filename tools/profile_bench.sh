@@ -57,7 +57,6 @@ python3 $R/tools/shard_emulate.py --cold 8 > $O/shard_emulate_cold_protocol.log 
 python3 $R/tools/shard_emulate.py --layouts 8 > $O/shard_emulate_layouts.log 2>&1
 python3 $R/tools/clock_ramp.py 10000 12500 300 > $O/clock_ramp.log 2>&1
 python3 $R/tools/clock_ramp.py 10000 12500 100 3 >> $O/clock_ramp.log 2>&1
-python3 $R/tools/encoder_mid.py > $O/encoder_mid.log 2>&1
 # round 6: what the prepared bank file is for (reference-schema float64 npz against .rbank, whole bank / a rank of 8)
 python3 $R/tools/load_time.py --dir /tmp/range_load_time --json $O/load_time.json > $O/load_time.log 2>&1
 rm -rf /tmp/range_load_time

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a range_topk_stream call's time goes: scan kernel / merge (separate launches with
 RANGE_TOPKS_FUSED=0, HIP-event pairs per kernel), for queries unrelated to the keys (the bench's)
-and queries that sit inside a crowd of similar keys.  RANGE_TOPKS_DIAG=1 prints candidate counts."""
+and queries that sit inside a crowd of similar keys."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -9,7 +9,6 @@ from range_amd import _native
 from tools.scan_bench import make_keys
 
 dev = torch.device("cuda:0")
-os.environ["RANGE_TOPKS_DIAG"] = "1"
 for n in (100_000, 1_000_000):
     keys = make_keys(n, dev)
     for fused in ("1", "0"):

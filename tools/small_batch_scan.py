@@ -37,7 +37,7 @@ for B, topk in (((16, 16), (32, 16), (64, 16)) if stream_only else
         us = ms / n * 1e3
         mms, mn = eng.profile_read(4)
         groups = (B + 15) // 16
-        G = int(os.environ.get('RANGE_TOPKS_GROUPS', '0')) or (1 if groups <= 1 else 2)
+        G = 1 if groups <= 1 else 2                                   # query groups per key pass
         passes = (groups + G - 1) // G
         t0 = time.perf_counter()
         for _ in range(50): eng.topk_stream(e32, topk)

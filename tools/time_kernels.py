@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel-tuning helper (GPU only): HIP-event times of the three kernels on the bench workload,
-no result checks (usable with deliberately broken experiment builds)."""
+no result checks."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
