@@ -1,4 +1,4 @@
-// Pure host arithmetic of the engine - launch geometry, the encoder's slot plan, recurrence
+// Pure host arithmetic of the engine - launch plans, the encoder's slot plan, recurrence
 // tables, weight packing - free of any HIP dependency, so that the same code the library runs is
 // also compiled with g++ under AddressSanitizer / UndefinedBehaviorSanitizer / ThreadSanitizer on
 // the CPU (tests/native/host_sanitize.cpp, tests/test_host_cpu.py).  GPU sanitizers are not
@@ -211,6 +211,328 @@ inline std::vector<double> pack_weights(const double* W, int n_out, int k_in, co
                     out[(((size_t)t * kp + s) * 64 + ln) * 2 + e] = k >= 0 ? W[(size_t)n * k_in + k] : 0.0;
                 }
     return out;
+}
+
+// ---- Launch plans: every number a launch site of range_hip.hip needs - which kernel variant, grid,
+// the argument fields derived from geometry, workspace sizes - as pure functions of integers and
+// switches.  range_hip.hip allocates, fills pointers and launches what a plan says;
+// tests/native/host_sanitize.cpp asks the plans the cases the comments below state.
+
+// Integer constants of the kernel headers that the plans need.  The kernel headers keep the only
+// definition of each; range_hip.hip fills this struct from them once (PLAN_CONSTS).
+struct PlanConsts {
+    int qtile, blk, val_dim, max_topk, p1_wg_per_cu;   // attend_kernels.h: QTILE, BLK, VAL_DIM, MAX_TOPK, P1_WG_PER_CU
+    int enc_qtile;                                     // encoder_kernel.h: ENC_QTILE
+    int topks_wl;                                      // topk_stream.h: TOPKS_WL
+    int tg_qblock, tg_wg_per_cu, tg_cap_l;             // topk_gemm.h: TG_QBLOCK, TG_WG_PER_CU, TG_CAP_L
+};
+
+// Small batches (fewer 16-query tiles than half the CUs): the first layer - 70 % of the weights
+// a workgroup streams - is split over S column parts per tile on S times as many workgroups
+// (encoder_l1_part_kernel), the rest follows per tile (encoder_rest_kernel).  One workgroup's
+// serial chain over all weights takes 0.28 ms whatever the batch; this pair takes about half.
+// the first layer's part kernels exist for parts of 64, 128, 256 and 512 columns
+inline bool split_width_ok(int H, int S) {
+    const int part = H / S;
+    return H % S == 0 && (part == 64 || part == 128 || part == 256 || part == 512);
+}
+
+// The small-batch encoder on `tiles` 16-query tiles with S x KP workgroups each.
+struct EncSplitPlan {
+    int tiles = 0, S = 1, KP = 1;
+    int part_cols = 0;          // first-layer columns of a part (H / S); the kernels are instantiated per part_cols / 64
+    int grid = 0;               // tiles * S * KP workgroups of the first (or only) launch
+    bool one_launch = false;    // encoder_tile_kernel: all phases in one persistent launch
+    int S2 = 1;                 // separate launches: second layer over S2 column parts per tile (1: inside the last kernel)
+    int n_parts2 = 0, part2_cols = 0;   // second-layer parts (one_launch or S2 > 1)
+    int rest_from = 0;          // EncArgs::rest_from of the last phase / launch
+    size_t h1_doubles = 0;      // partial sums of the first layer: KP * tiles * 16 * H
+    size_t tile_doubles = 0;    // a (tiles * 16, H) activation buffer (h1a, h2)
+};
+
+inline EncSplitPlan plan_encoder_split(int n_cu, int H, int n_layers, bool enc_fused, int64_t B, int S, int KP) {
+    EncSplitPlan p;
+    const int tiles = (int)((B + 15) / 16);
+    p.tiles = tiles;
+    p.S = S;
+    p.KP = KP;
+    p.part_cols = H / S;
+    p.grid = tiles * S * KP;
+    p.h1_doubles = (size_t)KP * tiles * 16 * H;
+    p.tile_doubles = (size_t)tiles * 16 * H;
+    // up to 32 tiles (512 queries): all phases in ONE launch (encoder_tile_kernel), every tile on its own
+    // workgroups, where a tile's first-layer workgroups are enough to carry its later phases (H / 64 of
+    // them the second layer, 4 the last)
+    // ... and, round 5, up to 128 tiles (2 048 queries: a rank's share of an 8-GPU batch, the last partial
+    // round of a large batch): the 2-7 workgroups a tile then gets take the parts of the later phases in
+    // turns (second-layer parts of 128 / 256 columns where a tile has < 8 / < 4 workgroups).  One launch
+    // against three (steady state): 513 queries 83 us / 114, 800: 93 / 118, 1 024:
+    // 102 / 122, 1 250: 128 / 132, 1 536 - 2 048: 155-156 / 157.  (The first version of this looked SLOWER
+    // beyond 816 queries and cost the <= 512-query path 15 us: per-part copies of the argument struct inside
+    // the phase loops had put 456 B of it into scratch memory - found through the latency log, now refused by
+    // tests/test_host_cpu.py.)  Phase stamps of a tile at 1 250 queries (us): first layer 49, wait 11,
+    // activation 4, second layer 21 (6 of them filling LDS), wait 10, last layer 16 (two parts of 64 outputs on
+    // the tile's first workgroup), norm 3.
+    const bool few_tiles = tiles <= 32 && S * KP >= std::max(std::max(H / 64, 4), (16 * H + 1023) / 1024);
+    const bool mid_tiles = tiles > 32 && tiles <= 128 && S * KP >= 2;
+    if ((few_tiles || mid_tiles) && n_layers == 2 && enc_fused && H % 64 == 0 && H <= 512 && tiles * S * KP <= n_cu) {
+        p.one_launch = true;
+        // second-layer parts: 64 columns where the tile has a workgroup for each, else 128 / 256
+        p.part2_cols = 64;
+        while (p.part2_cols < 256 && S * KP < H / p.part2_cols && H % (2 * p.part2_cols) == 0) p.part2_cols *= 2;
+        p.n_parts2 = H / p.part2_cols;
+        p.rest_from = 1;
+        return p;
+    }
+    // the second layer over S2 column parts per tile where there are CUs for it (and a second
+    // hidden layer exists); the last kernel then starts from its output.  Every part re-reads the
+    // tile's partial sums and re-activates them, and a third launch costs its ~10 us: measured
+    // (tools/encoder_latency.py, against two launches) 16 queries 106 -> 121 us, 256 queries
+    // equal, 625 queries 127 -> 118, 1 250 queries 145 -> 135, 2 048 queries 170 -> 162 us: from 32
+    // tiles on.
+    // A FEW tiles (up to 8: the latency regime - a handful of queries): one workgroup's chain over the
+    // second and the last layer is 12.6 MFLOP of float64 MFMA on ONE CU, 70-90 us whatever the batch.
+    // Splitting both layers there too (second: column parts; last: 4 parts of 64 outputs) with a
+    // one-wave-per-query kernel to normalise - four short launches instead of two - was MEASURED SLOWER:
+    // 133 us against 111 us for 16 queries (round 3; round 2 saw the same with three launches): every
+    // dependent launch costs ~10-20 us (dispatch, then 4-6 us before a kernel's first memory access
+    // returns), more than the split saves.  What helps is ONE persistent launch (encoder_tile_kernel above).
+    int S2 = 1;
+    for (int s2 = 2; s2 <= 8 && tiles >= 32 && tiles * s2 <= n_cu && n_layers >= 2; s2 *= 2) {
+        const int part = H / s2;
+        if (H % s2 == 0 && (part == 64 || part == 128 || part == 256)) S2 = s2;
+    }
+    p.S2 = S2;
+    if (S2 > 1) {
+        p.n_parts2 = S2;
+        p.part2_cols = H / S2;
+        p.rest_from = 1;
+    }
+    return p;
+}
+
+// A batch through the encoder: the leading main_B queries in one launch of encoder_kernel (n_wg32
+// workgroups of 32 queries, then workgroups of 16), the split_B queries behind them through the
+// small-batch kernels.  Either part may be empty.
+struct EncLaunchPlan {
+    int64_t main_B = 0;
+    int n_wg32 = 0, grid = 0;
+    int64_t split_B = 0;
+    EncSplitPlan split;
+};
+
+inline EncLaunchPlan plan_encoder(int n_cu, int n_slots, int H, int n_layers, bool enc_split, bool enc_fused,
+                                  int64_t B, int enc_qtile) {
+    EncLaunchPlan p;
+    // small batches: the first layer split over column parts and K ranges
+    int S, KP;
+    choose_encoder_split(n_cu, n_slots, H, (B + 15) / 16, S, KP);
+    if (S * KP > 1 && enc_split && split_width_ok(H, S)) {
+        p.split_B = B;
+        p.split = plan_encoder_split(n_cu, H, n_layers, enc_fused, B, S, KP);
+        return p;
+    }
+    const bool only16 = H > 512;       // (32 queries x H float64 of activations do not fit the LDS)
+    // Workgroups take 32 queries and cost the same, one per CU at a time.  When the last round of
+    // them would be less than half full, it is run with 16-query workgroups instead (about half
+    // the time each): 10 000 queries = 256 x 32 + 113 x 16 instead of 313 x 32.
+    const int64_t wg32 = (B + enc_qtile - 1) / enc_qtile;
+    const int64_t full_rounds = wg32 / n_cu;
+    const int64_t rem = B - full_rounds * n_cu * enc_qtile;      // queries after the full rounds
+    // A tail of up to 2 048 queries after full rounds runs as the small-batch kernels (its tiles
+    // spread over all CUs: ~0.16 ms for 1 808 queries) instead of a round of 16-query workgroups
+    // (0.23 ms whatever its fill): 10 000 queries = 256 x 32 + a split tail of 113 tiles.
+    auto main_plus_split_tail = [&](int64_t b_main) -> bool {       // false: not taken
+        const int64_t tail = B - b_main;
+        choose_encoder_split(n_cu, n_slots, H, (tail + 15) / 16, S, KP);
+        if (S * KP <= 1 || !split_width_ok(H, S)) return false;
+        // (whole rounds of equal workgroups: the plan of b_main queries is a main launch alone - a tail
+        // of its own would be a whole round of tiles, too many to split; host_sanitize.cpp sweeps that)
+        p = plan_encoder(n_cu, n_slots, H, n_layers, enc_split, enc_fused, b_main, enc_qtile);
+        p.split_B = tail;
+        p.split = plan_encoder_split(n_cu, H, n_layers, enc_fused, tail, S, KP);
+        return true;
+    };
+    if (full_rounds > 0 && rem > 0 && rem <= 2048 && enc_split && !only16 && main_plus_split_tail(B - rem)) return p;
+    // A batch a little over one round of 16-query workgroups (4 097 .. 5 376 queries on 256 CUs: what a rank
+    // of 2 encodes of BASELINE's batch) would fill 60 % of a round of 32-query workgroups and take that
+    // round's whole time (0.40 ms): a full round of 16-query workgroups (0.24 ms) + a split tail (<= 0.13 ms)
+    const int64_t round16 = (int64_t)16 * n_cu;
+    // (the same behind full rounds of 32-query workgroups: 8 192 k + 4 097 .. 5 376 queries)
+    if (rem > round16 && rem - round16 <= 1280 && enc_split && !only16 && main_plus_split_tail(B - (rem - round16))) return p;
+    p.main_B = B;
+    if (only16 || B <= (int64_t)16 * n_cu) {
+        // a batch that fits in one round either way: half-size workgroups on twice the CUs
+        p.n_wg32 = 0;
+        p.grid = (int)((B + 15) / 16);
+    } else if (full_rounds > 0 && rem > 0 && rem <= (int64_t)16 * n_cu) {
+        p.n_wg32 = (int32_t)(full_rounds * n_cu);
+        p.grid = p.n_wg32 + (int)((rem + 15) / 16);
+    } else {
+        p.n_wg32 = (int32_t)wg32;
+        p.grid = (int)wg32;
+    }
+    return p;
+}
+
+// Pass 1 (scan_stats_kernel) over a chunk of B queries, one workgroup per (bank split, query tile),
+// and the streaming top-k over the logits it kept.
+struct Pass1Plan {
+    int n_qtiles = 0, n_blocks = 0, n_splits = 0;
+    int grid = 0;               // n_splits * n_qtiles
+    bool merge_by_wave = false; // merge_stats_wave_kernel (one wave per query) instead of merge_stats_kernel
+    size_t part_floats = 0;     // statistics (and row maxima) per split: n_splits * B * 4
+    int64_t topk_slots = 0;     // top-k from the kept logits: wave slots of 16 queries ...
+    int topk_chunks = 0;        // ... x chunks of bank blocks; one candidate list per (chunk, query)
+};
+
+// topk_scan: the in-scan candidate lists (contexts that cannot keep logits); force_splits > 0: the
+// caller's split count (range_scan_stats_at), clamped to what the bank allows
+inline Pass1Plan plan_pass1(int n_cu, int64_t n_rows, int64_t B, bool topk_scan, int force_splits, const PlanConsts& K) {
+    Pass1Plan p;
+    p.n_blocks = (int32_t)((n_rows + K.blk - 1) / K.blk);
+    p.n_qtiles = (int32_t)((B + K.qtile - 1) / K.qtile);
+    // small batches are HBM-bound: many splits so that every CU streams a share of the keys
+    const bool few = B <= 4 * K.qtile;
+    // pass 1 writes 16 B per (query, split): many splits are free
+    // in-scan top-k candidates cost 512 B per (query, split) and are merged by one wave per
+    // query: keep the split count moderate in that variant
+    p.n_splits = choose_splits(p.n_qtiles, p.n_blocks, n_cu, K.p1_wg_per_cu,
+                               topk_scan ? (few ? 256 : 16) : (few ? 2048 : 128));
+    if (force_splits > 0) p.n_splits = std::max(1, std::min<int>(force_splits, std::max(1, p.n_blocks / 4)));
+    p.grid = p.n_splits * p.n_qtiles;
+    p.merge_by_wave = p.n_splits > 32;
+    p.part_floats = (size_t)p.n_splits * B * 4;
+    // enough waves to fill the chip: (B/16 wave slots) x chunks of bank blocks
+    p.topk_slots = (B + 15) / 16;
+    p.topk_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(
+        std::min<int64_t>(64, p.n_blocks / 32 > 0 ? p.n_blocks / 32 : 1),
+        ((int64_t)16 * n_cu + p.topk_slots - 1) / p.topk_slots));
+    return p;
+}
+
+// Pass 2 (attend_kernel / attend_stored_kernel / attend_bf16x3_kernel) over B queries.
+struct Pass2Plan {
+    int n_qtiles = 0, n_blocks = 0;
+    int n_splits = 0;           // split scheme: one workgroup per (bank split, query tile)
+    bool streamk = false;
+    int sk_cols = 1, sk_groups = 0;   // ScanArgs / SlabMap fields (split scheme: 1, 0)
+    int grid = 0;
+    size_t slab_floats = 0;     // the slabs the launch writes
+};
+
+// allow_streamk: RANGE_P2_STREAMK, and the kernel of this call has the walk (the exact ones)
+inline Pass2Plan plan_pass2(int n_cu, int64_t n_rows, int64_t B, bool allow_streamk, const PlanConsts& K) {
+    Pass2Plan p;
+    p.n_blocks = (int32_t)((n_rows + K.blk - 1) / K.blk);
+    p.n_qtiles = (int32_t)((B + K.qtile - 1) / K.qtile);
+    // pass 2 writes a 4 KB row
+    // (a small batch may split pass 2 further, until every CU has a workgroup).  Every extra
+    // split of pass 2 writes and re-reads a 4 KB row per query: 8 KB at ~4 TB/s against the
+    // query's MFMA time n_rows * 2054 FLOP / 140 TFLOP/s, i.e. 140 / n_rows of the launch - small
+    // for the whole bank on one GPU, 1 % per split for a 12 500-row shard.
+    p.n_splits = choose_splits(p.n_qtiles, p.n_blocks, n_cu, 1,
+                               std::max(32, std::min(512, (n_cu + p.n_qtiles - 1) / p.n_qtiles)),
+                               std::max(0.001, 140.0 / (double)n_rows));
+    // Stream-K (attend_kernels.h: SlabMap): as many workgroups as CUs, each with the same number of
+    // (query tile, bank block) units (at least 4: tiny launches take fewer workgroups), one slab per
+    // query tile a workgroup touches.  For banks and SHARDS of up to 50 000 rows - measured, 10 000
+    // queries, pass 2 + its reduction, against one workgroup per (split, query tile): 12 500 rows (a
+    // rank of 8) -5.6 %, 25 000 -3.6 %, 50 000 -2.2 %; at 100 000 rows that scheme's 7.97 rounds of
+    // workgroups are 98.5 % full already, the walk gains 0.5-1 % with two 50 000-row columns (and
+    // loses 9 % with one: its workgroups re-read the values from HBM then, not from the Infinity
+    // Cache) while its longer float32 accumulation chains cost accuracy (|sum of weights - 1| of the
+    // worst of 10^5 queries 1.3e-5 instead of 0.5e-5): not taken there.  The exact kernels only;
+    // RANGE_P2_STREAMK=0 restores the split scheme for A/B.
+    constexpr int P2_STREAMK_ROWS = 50000;
+    p.streamk = allow_streamk && n_rows <= P2_STREAMK_ROWS;
+    if (p.streamk) {
+        // columns of at most 16 384 rows: an accumulation chain (one query tile's blocks of a column)
+        // stays within ~2x the 481 blocks of the split scheme on the full bank
+        constexpr int P2_COL_ROWS = 16384;
+        p.sk_cols = (int32_t)std::max<int64_t>(1, std::min<int64_t>((n_rows + P2_COL_ROWS - 1) / P2_COL_ROWS,
+                                                                    std::max(1, p.n_blocks / 4)));
+        const int64_t Uc = (int64_t)p.n_qtiles * (p.n_blocks / p.sk_cols);     // (units of the shortest column)
+        p.sk_groups = (int32_t)std::max<int64_t>(1, std::min<int64_t>(n_cu, Uc / 4));
+        p.slab_floats = (size_t)p.sk_cols * (p.sk_groups + p.n_qtiles) * K.qtile * K.val_dim;
+    } else {
+        p.slab_floats = (size_t)p.n_splits * B * K.val_dim;
+    }
+    p.grid = p.streamk ? p.sk_groups : p.n_splits * p.n_qtiles;
+    return p;
+}
+
+// range_topk_stream: the batch-scale GEMM route (topk_gemm.h) or the persistent streaming scan
+// (topk_stream.h).
+struct TopkPlan {
+    int n_groups = 0, n_blocks = 0;   // query groups of 16, bank blocks
+    bool gemm = false;
+    // streaming scan
+    int G = 1;                  // query groups sharing one pass over the keys
+    int n_wg = 0;               // persistent grid
+    bool fused = false;         // the merge as the tail of the stream kernel
+    size_t cand_keys = 0, cand_dmax = 0;   // candidate lists / their bounds: one per (query, workgroup)
+    // GEMM route
+    int key_e2 = 0;             // key_norm_max < 2^key_e2: the fp16 copy of the keys is scaled by 2^(14 - key_e2)
+    int n_qblocks = 0, n_splits = 0, grid = 0;
+    int tile_stride = 1;        // pass A looks at every tile_stride-th tile
+};
+
+inline TopkPlan plan_topk(int n_cu, int64_t n_rows, int64_t B, float key_norm_max, bool topk_gemm, bool bf16,
+                          bool topks_fused, bool force_exact, int tg_sample, const PlanConsts& K) {
+    TopkPlan p;
+    p.n_groups = (int)((B + 15) / 16);
+    p.n_blocks = (int)((n_rows + K.blk - 1) / K.blk);
+    // persistent grid: one workgroup per CU (its key tiles fill the LDS), 4 waves each streaming
+    // its own tiles; one candidate list of 8 per (query, workgroup).  Query groups sharing one pass
+    // over the keys: 2 groups (32 queries) are still at the ridge (16 FLOP per key byte) and take
+    // the time of 1.3.
+    constexpr int NWV = 4;
+    // (the bf16 prefilter with FOUR groups per pass was measured too: one pass for 64 queries takes
+    // 27.0 us against 28.7 us for two passes of two groups - the list work per group, not the
+    // stream, is what a pass costs by then - and needs 370 registers; not kept)
+    p.G = p.n_groups <= 1 ? 1 : 2;     // query groups (of 16) sharing one pass over the keys
+    p.n_wg = std::max(1, std::min(std::min(n_cu, 256), (p.n_blocks + NWV - 1) / NWV));
+    // the merge runs as the tail of the stream kernel while every query finds a workgroup of its own
+    p.fused = topks_fused && B <= p.n_wg;
+    p.cand_keys = (size_t)p.n_groups * 16 * p.n_wg * K.topks_wl;
+    p.cand_dmax = (size_t)p.n_groups * 16 * p.n_wg;
+    // (the candidate lists of a call are addressed by 32-bit byte offsets: B x lists x 256 B < 4 GB - the
+    // Python layer calls in chunks of 16 384 queries = 1 GB at most)
+    // (a bank whose largest key norm is so far from 1 that no power of two brings it into fp16's range - or
+    // that is all zeros - keeps the streaming scan)
+    (void)std::frexp((double)key_norm_max, &p.key_e2);                  // key_norm_max < 2^e2
+    const bool tg_bank_ok = key_norm_max > 0.f && std::isfinite(key_norm_max) && std::abs(14 - p.key_e2) <= 100;
+    p.gemm = topk_gemm && bf16 && B > 256 && p.n_blocks >= 64 && !force_exact && B <= 60000 && tg_bank_ok;
+    if (p.gemm) {
+        // batches beyond the one-launch regime: GEMM-shaped, list-free (topk_gemm.h): group maxima ->
+        // per-query threshold -> candidates -> float32 re-rank.  Two workgroups per CU; the splits fill
+        // one round of them (at least 4: 32 row groups for the threshold; at least 8 tiles each).
+        p.n_qblocks = (int32_t)((B + K.tg_qblock - 1) / K.tg_qblock);
+        p.n_splits = std::max(4, std::min(std::min(K.tg_wg_per_cu * n_cu / p.n_qblocks, p.n_blocks / 8), 64));
+        p.grid = p.n_qblocks * p.n_splits;
+        p.tile_stride = std::max(1, std::min(tg_sample, p.n_blocks / p.n_splits / 4));
+    }
+    return p;
+}
+
+// range_forward of up to 32 queries: the whole retrieval in one pass over the bank (attend_small.h),
+// every workgroup its share of the bank blocks and all the queries (nq tiles of 16).
+struct SmallPlan {
+    int n_blocks = 0, n_wg = 0;
+    int nq = 1, qcap = 16;              // query tiles of a workgroup, queries they hold
+    size_t o_floats = 0, z_floats = 0;  // per-workgroup partial products (both heads) / weight sums
+};
+
+inline SmallPlan plan_forward_small(int n_cu, int64_t n_rows, int64_t B, const PlanConsts& K) {
+    SmallPlan p;
+    p.n_blocks = (int)((n_rows + K.blk - 1) / K.blk);
+    p.n_wg = std::max(1, std::min(n_cu, p.n_blocks));
+    p.nq = B > 16 ? 2 : 1;
+    p.qcap = 16 * p.nq;            // query tiles of a workgroup
+    p.o_floats = (size_t)p.n_wg * 2 * p.qcap * K.val_dim;
+    p.z_floats = (size_t)p.n_wg * p.qcap * 2;
+    return p;
 }
 
 }  // namespace range_host
