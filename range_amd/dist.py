@@ -27,23 +27,81 @@ same bank-split count, so a query's statistics - and the result - do not depend 
 The top-k side channel merges per-shard candidate lists with ONE all-gather (north star).
 
 Per-GPU work is B_total * N / W = B * N: adding GPUs adds queries at constant time per step
-(weak scaling).  The engine is duck-typed (see ``_native.HipEngine``) so that the collective
-logic can be exercised on CPU with the gloo backend and a checker engine in tests.
+(weak scaling).  The engine is duck-typed (``ShardEngine`` below; ``_native.HipEngine``) so that the
+collective logic can be exercised on CPU with the gloo backend and a checker engine in tests.
 """
 from __future__ import annotations
 
 import os
-from typing import Optional, Tuple
+from functools import partial
+from typing import Optional, Protocol, Tuple
 
 import torch
 import torch.distributed as dist
 
-from .range import TEMP_GEO, TEMP_RANGE, TEMP_RANGE_PLUS
+from .range import attend_any, range_model
 
 
 def shard_rows(n_rows: int, world_size: int, rank: int) -> Tuple[int, int]:
     """Contiguous, balanced row range of ``rank``."""
     return (n_rows * rank) // world_size, (n_rows * (rank + 1)) // world_size
+
+
+class ShardEngine(Protocol):
+    """What ``ShardedRange`` calls on its engine, over THIS rank's bank rows (``_native.HipEngine``
+    documents each; B = queries of the call, f32 / f64 tensors on the engine's device)."""
+
+    def encode(self, lonlat): ...                      # (B,2) f64 -> e64 (B,256) f64, e32 (B,256), xq (B,4)
+    def p1_splits(self, n_queries: int) -> int: ...    # bank splits pass 1 chooses for n_queries
+    def scan_stats_at(self, e32, xq, tau_sem, tau_geo, first_query, total_queries, n_splits=0): ...   # -> (B,4)
+    def kept_queries(self) -> int: ...                 # queries whose logits the current scan kept
+    def merge_stats(self, parts): ...                  # (W,B,4) -> (B,4), rank order
+    def attend(self, e32, xq, tau_sem, tau_geo, beta, stats): ...              # -> (B,1024) partial
+    def attend_kept(self, first_query, xq, tau_sem, tau_geo, beta, stats): ...  # the same, from kept logits
+    def blend(self, G, H, beta): ...                   # (1-beta) G + beta H, (B,1024)
+    def finalize(self, partials, e64, out=None): ...   # (W,B,1024), (B,256) f64 -> (B,1280) f64 (into ``out``)
+    def topk_stream(self, e32, k: int): ...            # -> values (B,k) f32, global rows (B,k) i64
+    def merge_topk(self, vals, idxs): ...              # (W,B,k) each -> (B,k) each
+
+
+def start_collective(kind: str, src: torch.Tensor, group=None, dst: Optional[torch.Tensor] = None,
+                     alloc=None):
+    """Start the collective ``kind`` of ``src`` asynchronously: "all_gather_into_tensor" ((n, ...) ->
+    (W*n, ...), rank-major: the concatenation form both RCCL and gloo accept) or "all_to_all_single"
+    (W equal slices, one direct transfer per peer).  Device tensors over the gloo backend (several
+    ranks sharing one GPU in tests, or a box without RCCL) travel as host copies; RCCL moves device
+    memory directly.  Received into ``dst`` (on ``src``'s device) when given, else into
+    ``alloc(shape, dtype, device)`` (default: a new tensor) on the device the collective runs on.
+    Returns (work, landed): once ``work.wait()`` has returned, ``landed()`` is the received tensor
+    on ``src``'s device (it also keeps the operands alive until then)."""
+    staged = src.is_cuda and dist.get_backend(group) == "gloo"
+    send = src.cpu() if staged else src.contiguous()
+    recv = dst
+    if dst is None or staged:
+        shape = tuple(src.shape) if dst is None else tuple(dst.shape)
+        if dst is None and kind == "all_gather_into_tensor":
+            shape = (dist.get_world_size(group) * shape[0],) + shape[1:]
+        recv = (alloc or (lambda s, t, d: torch.empty(s, dtype=t, device=d)))(shape, src.dtype, send.device)
+    work = getattr(dist, kind)(recv, send, group=group, async_op=True)
+
+    def landed(_keep=send):
+        if dst is None:
+            return recv.to(src.device)
+        return dst if recv is dst else dst.copy_(recv)
+    return work, landed
+
+
+def pack_topk(tv: torch.Tensor, ti: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Top-k candidates as ONE float32 buffer ``out`` (n,k,3): the values and the int64 rows' bit
+    patterns (2 x f32) - one collective instead of two."""
+    out[:, :, 0] = tv
+    out[:, :, 1:] = ti.view(torch.float32).reshape(tuple(tv.shape) + (2,))
+    return out
+
+
+def unpack_topk(buf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(..., k, 3) packed candidates -> contiguous values (..., k) float32 and rows (..., k) int64."""
+    return buf[..., 0].contiguous(), buf[..., 1:].contiguous().view(torch.int64).reshape(buf.shape[:-1])
 
 
 class ShardedRange:
@@ -61,13 +119,9 @@ class ShardedRange:
 
     def __init__(self, engine, model_name: str = "RANGE+", beta: Optional[float] = 0.5,
                  group=None, n_chunks: Optional[int] = None):
-        if model_name == "RANGE":
-            self.tau_sem, self.tau_geo, self.beta = TEMP_RANGE, 0.0, 1.0
-        elif model_name == "RANGE+":
-            self.tau_sem, self.tau_geo, self.beta = TEMP_RANGE_PLUS, TEMP_GEO, float(beta)
-        else:
-            raise ValueError("Unimplemented RANGE model")
-        self.engine = engine
+        self.tau_sem, self.tau_geo, _, _ = range_model(model_name)
+        self.beta = float(beta) if self.tau_geo else 1.0        # (RANGE: the semantic retrieval alone)
+        self.engine: ShardEngine = engine
         self.group = group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
@@ -77,9 +131,9 @@ class ShardedRange:
         self._bufs = {}
         self._timing = False
         self._events = {}
-        #: pass 1 per chunk with its collectives overlapped (needs engine.scan_stats_at); False: one
-        #: pass 1 over all scanned queries between a blocking gather and a blocking all-reduce (A/B, tests)
-        self.pass1_chunked = hasattr(engine, "scan_stats_at")
+        #: pass 1 per chunk with its collectives overlapped; False: one pass 1 over all scanned queries
+        #: between a blocking gather and a blocking all-reduce (A/B, tests)
+        self.pass1_chunked = True
         #: RANGE_DIST_BLOCKING=1: every collective is waited for where it is issued (no overlap with
         #: compute, one pass 1 over all scanned queries) - the escape hatch for bisecting a hang or a
         #: wrong result on a backend the overlapped schedule has not met (it has run over gloo and
@@ -145,42 +199,32 @@ class ShardedRange:
         self._events.setdefault(kind, []).append((a, b))
         return r
 
-    def _staged(self, t: torch.Tensor) -> bool:
-        """Device tensors over the gloo backend (several ranks sharing one GPU in tests, or a box
-        without RCCL): the collective runs on host copies.  RCCL moves device memory directly."""
-        return t.is_cuda and dist.get_backend(self.group) == "gloo"
+    def _start(self, kind: str, src: torch.Tensor, key: str, timed: Optional[str],
+               dst: Optional[torch.Tensor] = None, name: Optional[str] = None):
+        """The one way a collective is issued here (``start_collective``): counts its payload under
+        ``key``, starts it asynchronously - received into ``dst``, else into the buffer ``name`` - and
+        returns the function that makes the current stream wait for it and yields the received tensor
+        on ``src``'s device.  The wait runs under ``_blocked(timed, ...)`` (``timed=None``: untimed,
+        the caller times it).  ``blocking``: waited for here, where it is issued; the returned
+        function then only lands the result."""
+        nb = src.numel() * src.element_size() // (self.world if kind == "all_to_all_single" else 1)
+        self._count(key, nb * (self.world - 1), nb * (self.world - 1))
+        work, landed = start_collective(kind, src, self.group, dst, name and partial(self._buf, name))
+        wait = (lambda: self._blocked(timed, work.wait)) if timed else work.wait
+        if self.blocking:
+            wait()
+            return landed
+
+        def result():
+            wait()
+            return landed()
+        return result
 
     def _gather(self, t: torch.Tensor, name: str) -> torch.Tensor:
-        # concatenation form (W*n, ...): accepted by both the RCCL and the gloo backend
-        src = t.contiguous()
-        if self._staged(t):
-            src = src.cpu()
-        out = self._buf("gather:" + name, (self.world * t.shape[0],) + tuple(t.shape[1:]), t.dtype,
-                        src.device)
-        self._blocked("gather", lambda: dist.all_gather_into_tensor(out, src, group=self.group))
-        nb = src.numel() * src.element_size()
-        self._count("gather", nb * (self.world - 1), nb * (self.world - 1))
-        return out.to(t.device).reshape((self.world,) + tuple(t.shape))
-
-    def _gather_start(self, src: torch.Tensor, dst: torch.Tensor):
-        """Start the all-gather of ``src`` (n, d) into ``dst`` (W*n, d), rank-major: returns a
-        function that makes the current stream wait for it (and, staged, lands the host copy)."""
-        nb = src.numel() * src.element_size()
-        self._count("gather", nb * (self.world - 1), nb * (self.world - 1))
-        if self._staged(src):
-            h_src = src.cpu()
-            h_dst = torch.empty(dst.shape, dtype=dst.dtype)
-            work = dist.all_gather_into_tensor(h_dst, h_src, group=self.group, async_op=True)
-
-            def land():
-                work.wait()
-                dst.copy_(h_dst)
-            return land
-        work = dist.all_gather_into_tensor(dst, src.contiguous(), group=self.group, async_op=True)
-        if self.blocking:
-            work.wait()
-            return lambda: None
-        return work.wait
+        """Blocking all-gather of ``t`` -> (W, *t.shape); the time from its issue on counts as exposed."""
+        out = self._blocked("gather", lambda: self._start("all_gather_into_tensor", t, "gather", None,
+                                                          name="gather:" + name)())
+        return out.reshape((self.world,) + tuple(t.shape))
 
     def _stats_start(self, stats: torch.Tensor, name: str):
         """Start the all-gather of a chunk's statistics (n,4) and return the function that waits for
@@ -191,44 +235,14 @@ class ShardedRange:
         chunking and of the collective algorithm (16 B per scanned query to every peer, one small
         kernel).  Counted and timed under the key "reduce" (what it replaces); the time is the
         wait for the collective alone, not the merge kernel behind it."""
-        out = self._buf("gather:" + name, (self.world * stats.shape[0], stats.shape[1]), stats.dtype,
-                        torch.device("cpu") if self._staged(stats) else stats.device)
-        nb = stats.numel() * stats.element_size()
-        self._count("reduce", nb * (self.world - 1), nb * (self.world - 1))
-        src = stats.cpu() if self._staged(stats) else stats
-        work = dist.all_gather_into_tensor(out, src, group=self.group, async_op=True)
-        if self.blocking:
-            self._blocked("reduce", work.wait)
+        got = self._start("all_gather_into_tensor", stats, "reduce", "reduce", name="gather:" + name)
+        return lambda: self.engine.merge_stats(got().view((self.world,) + tuple(stats.shape)))
 
-        def merged():
-            if not self.blocking:
-                self._blocked("reduce", work.wait)
-            parts = out.to(stats.device).view(self.world, stats.shape[0], stats.shape[1])
-            return self.engine.merge_stats(parts)
-        return merged
-
-    def _all_to_all(self, part: torch.Tensor, name: str):
-        """Start the exchange of a chunk's partials; returns (work, getter of the received tensor)."""
-        nb = part.numel() * part.element_size() // self.world * (self.world - 1)
-        self._count("exchange", nb, nb)
-        if self._staged(part):
-            src = part.cpu()
-            recv = torch.empty_like(src)
-            work = dist.all_to_all_single(recv, src, group=self.group, async_op=True)
-            return work, (lambda: recv.to(part.device)), src
-        recv = self._buf("recv:" + name, part.shape, part.dtype, part.device)
-        # one direct transfer per peer; asynchronous, so that the exchange of this chunk
-        # overlaps pass 2 of the next
-        work = dist.all_to_all_single(recv, part, group=self.group, async_op=True)
-        if self.blocking:
-            self._blocked("exchange", work.wait)
-        return work, (lambda: recv), part
-
-    def _reduce_stats(self, stats_local: torch.Tensor) -> torch.Tensor:
-        """Global softmax statistics from the shards' (the blocking form of the unchunked pass 1):
-        every shard reports (m, l) with the SAME constant shift m (range_hip.h: range_scan_stats),
-        so the sums l of disjoint row sets add - gathered and merged in rank order (``_stats_start``)."""
-        return self._stats_start(stats_local, "stats")()
+    def _exchange(self, part: torch.Tensor, name: str):
+        """Start the all-to-all of a chunk's partials (asynchronous, so that the exchange of this
+        chunk overlaps pass 2 of the next); returns the function that waits for it and yields the W
+        slices received."""
+        return self._start("all_to_all_single", part, "exchange", "exchange", name="recv:" + name)
 
     def _gather_queries(self, lonlat: torch.Tensor):
         """Encode the own queries and gather every rank's scan operands: e32 (B,256) and xq (B,4)
@@ -282,15 +296,10 @@ class ShardedRange:
             e32_all = self._chunk_major(e32_all, chunks, "e32")
             xq_all = self._chunk_major(xq_all, chunks, "xq")
             n_max = W * max(hi - lo for lo, hi in chunks)
-            if hasattr(eng, "scan_stats_at"):
-                # (the same bank splits as the chunked form: bit-identical statistics)
-                stats_local = eng.scan_stats_at(e32_all, xq_all, self.tau_sem, self.tau_geo, 0, W * B,
-                                                n_splits=eng.p1_splits(n_max))
-            else:
-                # pass 1 on the local shard keeps its logits; pass 2 reads them back instead of
-                # recomputing e . K^T (they are independent of the global statistics)
-                stats_local = eng.scan_stats(e32_all, xq_all, self.tau_sem, self.tau_geo, keep_logits=True)
-            stats = self._reduce_stats(stats_local)
+            # (the same bank splits as the chunked form: bit-identical statistics)
+            stats_local = eng.scan_stats_at(e32_all, xq_all, self.tau_sem, self.tau_geo, 0, W * B,
+                                            n_splits=eng.p1_splits(n_max))
+            stats = self._stats_start(stats_local, "stats")()
             getters = [(lambda lo=lo, hi=hi: stats[W * lo:W * hi]) for lo, hi in chunks]
             return e64, e32_all, xq_all, chunks, getters, eng.kept_queries() == W * B
         e64, e32, xq = eng.encode(lonlat)
@@ -298,9 +307,10 @@ class ShardedRange:
         e32_all = self._buf("cm:e32", (total, e32.shape[1]), e32.dtype, e32.device)
         xq_all = self._buf("cm:xq", (total, xq.shape[1]), xq.dtype, xq.device)
         # every chunk's gather is issued now: a chunk's rows of all ranks land rank-major in rows
-        # [W lo, W hi) - the chunk-major order of the scan, no copy
-        landed = [(self._gather_start(e32[lo:hi], e32_all[W * lo:W * hi]),
-                   self._gather_start(xq[lo:hi], xq_all[W * lo:W * hi])) for lo, hi in chunks]
+        # [W lo, W hi) - the chunk-major order of the scan, no copy.  (Their waits are timed HERE, in
+        # the loop below; a ``blocking`` gather has been waited for at its issue, untimed)
+        landed = [tuple(self._start("all_gather_into_tensor", t[lo:hi], "gather", None, dst=t_all[W * lo:W * hi])
+                        for t, t_all in ((e32, e32_all), (xq, xq_all))) for lo, hi in chunks]
         n_splits = eng.p1_splits(W * max(hi - lo for lo, hi in chunks))
         getters = []
         for (lo, hi), (we, wx) in zip(chunks, landed):
@@ -309,8 +319,7 @@ class ShardedRange:
             first, n = W * lo, W * (hi - lo)
             st = eng.scan_stats_at(e32_all[first:first + n], xq_all[first:first + n], self.tau_sem, self.tau_geo,
                                    first, total, n_splits=n_splits)
-            merged = self._stats_start(st, f"stats{len(getters)}")
-            getters.append(merged)
+            getters.append(self._stats_start(st, f"stats{len(getters)}"))
         return e64, e32_all, xq_all, chunks, getters, eng.kept_queries() == total
 
     def _topk_start(self, e32_all: torch.Tensor, chunks, k: int):
@@ -319,30 +328,17 @@ class ShardedRange:
         the ONE all-gather of the packed candidates (north star); returns the function that waits for
         it and merges this rank's OWN queries' W lists (global rows, ties to the lower row)."""
         W, total = self.world, e32_all.shape[0]
-        B = total // W
         # (the keys-only scan: it leaves the logits pass 1 kept for pass 2 alone)
         tv, ti = self.engine.topk_stream(e32_all, k)
-        packed = self._buf("pack:topk", (total, k, 3), torch.float32, tv.device)
-        packed[:, :, 0] = tv
-        packed[:, :, 1:] = ti.view(torch.float32).reshape(total, k, 2)          # int64 bit pattern
-        staged = self._staged(packed)
-        src = packed.cpu() if staged else packed
-        allp = self._buf("gather:fwd_topk", (W * total, k, 3), torch.float32, src.device)
-        nb = src.numel() * src.element_size()
-        self._count("topk", nb * (W - 1), nb * (W - 1))
-        work = dist.all_gather_into_tensor(allp, src, group=self.group, async_op=True)
-        if self.blocking:
-            self._blocked("gather", work.wait)
+        packed = pack_topk(tv, ti, self._buf("pack:topk", (total, k, 3), torch.float32, tv.device))
+        # (counted as "topk"; its wait is timed with the gathers)
+        got = self._start("all_gather_into_tensor", packed, "topk", "gather", name="gather:fwd_topk")
 
         def merged():
-            if not self.blocking:
-                self._blocked("gather", work.wait)
-            a = allp.to(tv.device).view(W, total, k, 3)
+            a = got().view(W, total, k, 3)
             # this rank's rows of the chunk-major order: chunk (lo,hi) holds them at W lo + rank (hi - lo)
             own = torch.cat([a[:, W * lo + self.rank * (hi - lo):W * lo + (self.rank + 1) * (hi - lo)] for lo, hi in chunks], dim=1)
-            vals = own[..., 0].contiguous()
-            idxs = own[..., 1:].contiguous().view(torch.int64).reshape(W, B, k)
-            return self.engine.merge_topk(vals, idxs)
+            return self.engine.merge_topk(*unpack_topk(own))
         return merged
 
     @torch.no_grad()
@@ -359,25 +355,13 @@ class ShardedRange:
         pending = []
         for ci, (lo, hi) in enumerate(chunks):
             first, n = W * lo, W * (hi - lo)
-            stats = stats_of[ci]()
-            if kept:
-                part = self.engine.attend_kept(first, xq_all[first:first + n], self.tau_sem,
-                                               self.tau_geo, self.beta, stats)
-            else:
-                part = self.engine.attend(e32_all[first:first + n], xq_all[first:first + n],
-                                          self.tau_sem, self.tau_geo, self.beta, stats)
-            work, get, keep = self._all_to_all(part, f"fwd{ci}")
-            pending.append((work, get, keep, lo, hi))
+            part = attend_any(self.engine, kept, first, e32_all[first:first + n], xq_all[first:first + n],
+                              self.tau_sem, self.tau_geo, self.beta, stats_of[ci]())
+            pending.append((self._exchange(part, f"fwd{ci}"), lo, hi))
         if out is None:
             out = torch.empty((lonlat.shape[0], e64.shape[1] + 1024), dtype=torch.float64, device=e64.device)
-        into = hasattr(self.engine, "scan_stats_at")      # (engines of the round-3 duck type return a new tensor)
-        for work, get, keep, lo, hi in pending:
-            self._blocked("exchange", work.wait)
-            recv = get().reshape(W, hi - lo, -1)
-            if into:
-                self.engine.finalize(recv, e64[lo:hi], out=out[lo:hi])
-            else:
-                out[lo:hi] = self.engine.finalize(recv, e64[lo:hi].contiguous())
+        for received, lo, hi in pending:
+            self.engine.finalize(received().reshape(W, hi - lo, -1), e64[lo:hi], out=out[lo:hi])
         if topk_of is not None:
             tv, ti = topk_of()
             return out, tv, ti
@@ -499,22 +483,13 @@ class ShardedRange:
             first, n = W * lo, W * (hi - lo)
             sl = slice(first, first + n)
             st = stats_of[ci]()
-            parts = []
-            for b in (1.0, 0.0):
-                if kept:
-                    parts.append(self.engine.attend_kept(first, xq_all[sl], self.tau_sem,
-                                                         self.tau_geo, b, st))
-                else:
-                    parts.append(self.engine.attend(e32_all[sl], xq_all[sl], self.tau_sem,
-                                                    self.tau_geo, b, st))
-            ex = [self._all_to_all(p, f"sweep{ci}:{j}") for j, p in enumerate(parts)]
-            pending.append((ex, lo, hi))
+            parts = [attend_any(self.engine, kept, first, e32_all[sl], xq_all[sl], self.tau_sem, self.tau_geo, b, st)
+                     for b in (1.0, 0.0)]
+            pending.append(([self._exchange(p, f"sweep{ci}:{j}") for j, p in enumerate(parts)], lo, hi))
         out = torch.empty((len(betas), B, e64.shape[1] + 1024), dtype=torch.float64,
                           device=e64.device)
-        for ex, lo, hi in pending:
-            for work, _, _ in ex:
-                self._blocked("exchange", work.wait)
-            rH, rG = ex[0][1](), ex[1][1]()
+        for (got_h, got_g), lo, hi in pending:
+            rH, rG = got_h(), got_g()
             e = e64[lo:hi].contiguous()
             for j, b in enumerate(betas):
                 mix = self.engine.blend(rG, rH, b)                   # (W*n, 1024): per-shard partials
@@ -526,22 +501,12 @@ class ShardedRange:
         """Global top-k (semantic cosine similarity) for this rank's queries: per-shard top-k,
         one all-gather of the candidates, k-way merge."""
         W, B = self.world, lonlat.shape[0]
-        _, e32_all, xq_all = self._gather_queries(lonlat)
-        e32_all, xq_all = e32_all.contiguous(), xq_all.contiguous()
-        if hasattr(self.engine, "topk_stream"):
-            # the HBM-streaming kernel: faster than pass 1's own top-k at every batch size
-            tv, ti = self.engine.topk_stream(e32_all, k)
-        else:
-            _, tv, ti = self.engine.scan_stats(e32_all, xq_all, self.tau_sem, 0.0, topk=k)
-        # values and int64 indices travel in one buffer (index bit patterns viewed as 2 x f32)
-        packed = torch.empty((W * B, k, 3), dtype=torch.float32, device=tv.device)
-        packed[:, :, 0] = tv
-        packed[:, :, 1:] = ti.view(torch.float32).reshape(W * B, k, 2)   # int64 bit pattern
+        _, e32_all, _ = self._gather_queries(lonlat)
+        # the HBM-streaming kernel: faster than pass 1's own top-k at every batch size
+        tv, ti = self.engine.topk_stream(e32_all.contiguous(), k)
+        packed = pack_topk(tv, ti, self._buf("pack:topk", (W * B, k, 3), torch.float32, tv.device))
         allp = self._gather(packed, "topk")                                    # the ONE all-gather
-        sl = slice(self.rank * B, (self.rank + 1) * B)
-        vals = allp[:, sl, :, 0].contiguous()
-        idxs = allp[:, sl, :, 1:].contiguous().view(torch.int64).reshape(W, B, k)
-        return self.engine.merge_topk(vals, idxs)
+        return self.engine.merge_topk(*unpack_topk(allp[:, self.rank * B:(self.rank + 1) * B]))
 
 
 def make_layout(row_shards: int, group=None):

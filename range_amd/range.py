@@ -45,6 +45,54 @@ def _device_of(spec) -> torch.device:
     return dev
 
 
+def range_model(name: str):
+    """"RANGE" / "RANGE+" -> (tau_sem, tau_geo, kernel model id, the reference's banner); tau_geo = 0:
+    no geographic retrieval."""
+    if name == "RANGE":                                                 # range.py:102-105
+        return TEMP_RANGE, 0.0, _native.MODEL_RANGE, f"Using RANGE with temperature {TEMP_RANGE}"
+    if name == "RANGE+":                                                # :107-112
+        return (TEMP_RANGE_PLUS, TEMP_GEO, _native.MODEL_RANGE_PLUS,
+                f"Using RANGE+ with temperatures {TEMP_RANGE_PLUS} and {TEMP_GEO}")
+    raise ValueError("Unimplemented RANGE model")                       # :113-114
+
+
+def attend_any(eng, kept: bool, first: int, e32, xq, tau_sem, tau_geo, beta, stats):
+    """Pass 2 for queries [first, first + len(xq)) of the last scan: from its logits when the scan
+    kept them (``kept``), else recomputed from their e-hat ``e32`` - bit-identical partials."""
+    if kept:
+        return eng.attend_kept(first, xq, tau_sem, tau_geo, beta, stats)
+    return eng.attend(e32, xq, tau_sem, tau_geo, beta, stats)
+
+
+def _as_coords(coords, device) -> torch.Tensor:
+    if not torch.is_tensor(coords):
+        coords = torch.as_tensor(np.asarray(coords))
+    if coords.dim() != 2 or coords.shape[1] != 2:
+        raise ValueError(f"coords must be (B,2) (lon,lat) degrees, got {tuple(coords.shape)}")
+    # the reference requires float64 input (F.linear against .double() weights);
+    # float32 input is accepted here by widening
+    return coords.to(device=device, dtype=torch.float64).contiguous()
+
+
+def _topk_arg(return_topk, has_bank: bool = True) -> int:
+    k = int(return_topk)
+    if not has_bank:
+        raise ValueError("return_topk needs a bank (RANGE / RANGE+)")
+    if not 1 <= k <= _native.MAX_TOPK:
+        raise ValueError(f"return_topk must be in 1..{_native.MAX_TOPK}, got {return_topk}")
+    return k
+
+
+def _load(args, with_bank: bool):
+    """The bank (``with_bank``) and the encoder checkpoint ``args`` name; both 256 wide."""
+    bank = load_bank(args.range_db) if with_bank else None              # range.py:78-95
+    enc = read_checkpoint(args.pretrained_path)                         # :82-84
+    if enc.embed_dim != 256:
+        raise ValueError(f"checkpoint embed_dim {enc.embed_dim}" +
+                         (" != bank key width 256" if with_bank else ": only 256 is implemented"))
+    return bank, enc
+
+
 _SH_TABLES = {}     # (L, source path or None) -> SHTable
 
 
@@ -130,11 +178,7 @@ class SatCLIPLocationModel(nn.Module):
     @torch.no_grad()
     def forward(self, coords: torch.Tensor) -> torch.Tensor:
         eng = self._engine[0]
-        if not torch.is_tensor(coords):
-            coords = torch.as_tensor(np.asarray(coords))
-        if coords.dim() != 2 or coords.shape[1] != 2:
-            raise ValueError(f"coords must be (B,2) (lon,lat) degrees, got {tuple(coords.shape)}")
-        x = coords.to(device=eng.device, dtype=torch.float64).contiguous()
+        x = _as_coords(coords, eng.device)
         if x.shape[0] == 0:
             return torch.empty((0, 256), dtype=torch.float64, device=x.device)
         parts = [eng.encode_raw(x[i:i + self._chunk]) for i in range(0, x.shape[0], self._chunk)]
@@ -159,7 +203,35 @@ class _CoordLocationModel(nn.Module):
         return eng.coord_features(x, _native.COORD_WRAP) if x.shape[0] else torch.empty((0, 4), dtype=torch.float64, device=x.device)
 
 
-class LocationEncoder(nn.Module):
+class _EncoderBase(nn.Module):
+    """What the one-GPU and the row-sharded encoder share: ``args``, ``engine``, ``loc_model``."""
+
+    def _range_temperatures(self) -> int:
+        """``args.temp`` / ``args.geo_temp`` and the banner of RANGE / RANGE+; returns the kernel model id."""
+        self.args.temp, tau_geo, model_id, banner = range_model(self.location_model_name)
+        if tau_geo:
+            self.args.geo_temp = tau_geo
+        print(banner)
+        return model_id
+
+    def _make_engine(self, enc, bank, row_offset: int = 0):
+        a = self.args
+        self._device = _device_of(a.device)
+        return make_engine(enc, bank, self._device, row_offset, sh_eval=getattr(a, "sh_eval", None),
+                           sh_source=getattr(a, "sh_source", None),
+                           pv_mode=getattr(a, "pv_mode", None) if bank is not None else None)
+
+    def _freeze(self):
+        self.loc_model.eval()                                               # range.py:201-203
+        for params in self.loc_model.parameters():
+            params.requires_grad = False
+        self.eval()
+
+    def _coords(self, coords) -> torch.Tensor:
+        return _as_coords(coords, self.engine.device)
+
+
+class LocationEncoder(_EncoderBase):
     """RANGE / RANGE+ retrieval-augmented location encoder (reference: range/range.py:69)."""
 
     #: queries per engine call; bounds the per-call workspace (split slabs of chunk x 4 KB)
@@ -175,40 +247,20 @@ class LocationEncoder(nn.Module):
         self.args = args
         self.location_model_name = args.location_model_name
         if "RANGE" in self.location_model_name:                        # range.py:76
-            bank = load_bank(args.range_db)                            # :78-95
-            enc = read_checkpoint(args.pretrained_path)                # :82-84
-            if enc.embed_dim != 256:
-                raise ValueError(f"checkpoint embed_dim {enc.embed_dim} != bank key width 256")
+            bank, enc = _load(args, with_bank=True)
             self.location_feature_dim = 1024 + 256                     # :86
-            if self.location_model_name == "RANGE":                    # :102-105
-                self.args.temp = TEMP_RANGE
-                self._model_id = _native.MODEL_RANGE
-                print(f"Using RANGE with temperature {self.args.temp}")
-            elif self.location_model_name == "RANGE+":                 # :107-112
-                self.args.geo_temp = TEMP_GEO
-                self.args.temp = TEMP_RANGE_PLUS
-                self._model_id = _native.MODEL_RANGE_PLUS
-                print(f"Using RANGE+ with temperatures {self.args.temp} and {self.args.geo_temp}")
-            else:
-                raise ValueError("Unimplemented RANGE model")           # :113-114
+            self._model_id = self._range_temperatures()
             self.encoder_params = enc
             self.n_bank_rows = bank.n_rows
-            self._device = _device_of(args.device)
-            self.engine = make_engine(enc, bank, self._device, sh_eval=getattr(args, "sh_eval", None),
-                                      sh_source=getattr(args, "sh_source", None),
-                                      pv_mode=getattr(args, "pv_mode", None))
+            self.engine = self._make_engine(enc, bank)
             self.loc_model = SatCLIPLocationModel(self.engine, enc, self.chunk_size)   # :83-84
         elif self.location_model_name == "SatCLIP":                     # range.py:117-122
             print("Using SatCLIP")
-            enc = read_checkpoint(args.pretrained_path)
-            if enc.embed_dim != 256:
-                raise ValueError(f"checkpoint embed_dim {enc.embed_dim}: only 256 is implemented")
+            _, enc = _load(args, with_bank=False)
             self.location_feature_dim = 256
             self._model_id = None
             self.encoder_params = enc
-            self._device = _device_of(args.device)
-            self.engine = make_engine(enc, None, self._device, sh_eval=getattr(args, "sh_eval", None),
-                                      sh_source=getattr(args, "sh_source", None))
+            self.engine = self._make_engine(enc, None)
             self.loc_model = SatCLIPLocationModel(self.engine, enc, self.chunk_size)   # :119-121
         elif self.location_model_name in _COORD_MODELS:                 # range.py:152-162, 170-173
             mode, banner = _COORD_MODELS[self.location_model_name]
@@ -224,19 +276,7 @@ class LocationEncoder(nn.Module):
             # Theory, sphere2vec; range.py:124-198): third-party pretrained baselines, out of
             # scope for this engine
             raise NotImplementedError(f"{self.location_model_name} not implemented")
-        self.loc_model.eval()                                               # range.py:201-203
-        for params in self.loc_model.parameters():
-            params.requires_grad = False
-        self.eval()
-
-    def _coords(self, coords) -> torch.Tensor:
-        if not torch.is_tensor(coords):
-            coords = torch.as_tensor(np.asarray(coords))
-        if coords.dim() != 2 or coords.shape[1] != 2:
-            raise ValueError(f"coords must be (B,2) (lon,lat) degrees, got {tuple(coords.shape)}")
-        # the reference requires float64 input (F.linear against .double() weights);
-        # float32 input is accepted here by widening
-        return coords.to(device=self.engine.device, dtype=torch.float64).contiguous()
+        self._freeze()
 
     @torch.no_grad()
     def forward(self, coords, return_device: bool = False, return_topk: Optional[int] = None):
@@ -253,12 +293,7 @@ class LocationEncoder(nn.Module):
         x = self._coords(coords)
         B = x.shape[0]
         if return_topk is not None:
-            k = int(return_topk)
-            if self._model_id is None:
-                raise ValueError("return_topk needs a bank (RANGE / RANGE+)")
-            if not 1 <= k <= _native.MAX_TOPK:
-                raise ValueError(f"return_topk must be in 1..{_native.MAX_TOPK}, got {return_topk}")
-            return self._forward_with_topk(x, k, return_device)
+            return self._forward_chunks(x, return_device, _topk_arg(return_topk, self._model_id is not None))
         if getattr(self, "_coord_mode", None) is not None:
             # Direct / Wrap return a device tensor, Cartesian_3D a host ndarray (its rad_to_cart
             # runs in numpy, range.py:265-268)
@@ -275,43 +310,32 @@ class LocationEncoder(nn.Module):
                 return torch.empty((0, 256), dtype=torch.float64, device=x.device)
             return torch.cat([self.engine.encode_raw(x[i:i + self.chunk_size])
                               for i in range(0, B, self.chunk_size)])
-        beta = 1.0 if self._model_id == _native.MODEL_RANGE else float(self.args.beta)
-        # (B == 0: nothing to launch; the reference returns an empty (0,1280) array as well)
-        if not return_device:
-            # the reference's contract: a fresh host array (range.py:240), filled slab by slab
-            # while the device->host copies of later slabs are in flight (range_forward_host)
-            host = POOL.take(B, _native.OUT_DIM)
-            for i in range(0, B, self.chunk_size):
-                self.engine.forward_host(x[i:i + self.chunk_size], self._model_id, beta,
-                                         out=host[i:i + self.chunk_size])
-            return host
-        out = torch.empty((B, _native.OUT_DIM), dtype=torch.float64, device=x.device)
-        for i in range(0, B, self.chunk_size):
-            self.engine.forward(x[i:i + self.chunk_size], self._model_id, beta,
-                                out=out[i:i + self.chunk_size])
-        return out
+        return self._forward_chunks(x, return_device)
 
-    def _forward_with_topk(self, x: torch.Tensor, k: int, return_device: bool):
+    def _forward_chunks(self, x: torch.Tensor, return_device: bool, k: Optional[int] = None):
+        """The RANGE / RANGE+ forward in ``chunk_size`` slices, into a device tensor or
+        (``return_device=False``, the reference's contract: range.py:240) a fresh host array filled slab by
+        slab while the device->host copies of later slabs are in flight (range_forward_host); ``k``: with
+        the top-k of every slice -> (out, values, rows).  (B == 0: nothing to launch; the reference returns
+        an empty (0,1280) array as well)"""
         B = x.shape[0]
         beta = 1.0 if self._model_id == _native.MODEL_RANGE else float(self.args.beta)
-        tv = torch.empty((B, k), dtype=torch.float32, device=x.device)
-        ti = torch.empty((B, k), dtype=torch.int64, device=x.device)
         if return_device:
-            out = torch.empty((B, _native.OUT_DIM), dtype=torch.float64, device=x.device)
+            run, out = self.engine.forward, torch.empty((B, _native.OUT_DIM), dtype=torch.float64, device=x.device)
         else:
-            out = POOL.take(B, _native.OUT_DIM)
+            run, out = self.engine.forward_host, POOL.take(B, _native.OUT_DIM)
+        if k:
+            tv = torch.empty((B, k), dtype=torch.float32, device=x.device)
+            ti = torch.empty((B, k), dtype=torch.int64, device=x.device)
         for i in range(0, B, self.chunk_size):
             xc = x[i:i + self.chunk_size]
             n = xc.shape[0]
-            if return_device:
-                self.engine.forward(xc, self._model_id, beta, out=out[i:i + n])
-            else:
-                self.engine.forward_host(xc, self._model_id, beta, out=out[i:i + n])
-            # (behind the forward on the same stream: the host result above is complete, the scan of
-            # this chunk's e-hat runs while the caller - or the next chunk's encoder launch - goes on)
-            v, j = self.engine.topk_last(n, k)
-            tv[i:i + n], ti[i:i + n] = v, j
-        return out, tv, ti
+            run(xc, self._model_id, beta, out=out[i:i + n])
+            if k:
+                # (behind the forward on the same stream: the host result above is complete, the scan of
+                # this chunk's e-hat runs while the caller - or the next chunk's encoder launch - goes on)
+                tv[i:i + n], ti[i:i + n] = self.engine.topk_last(n, k)
+        return (out, tv, ti) if k else out
 
     @torch.no_grad()
     def sweep(self, coords, betas, return_device: bool = False):
@@ -330,12 +354,8 @@ class LocationEncoder(nn.Module):
         for i in range(0, B, self.chunk_size):
             e64, e32, xq = eng.encode(x[i:i + self.chunk_size])
             st = eng.scan_stats(e32, xq, TEMP_RANGE_PLUS, TEMP_GEO, keep_logits=True)
-            if eng.kept_queries() == e32.shape[0]:      # both passes 2 from the kept logits
-                H = eng.attend_kept(0, xq, TEMP_RANGE_PLUS, TEMP_GEO, 1.0, st)
-                G = eng.attend_kept(0, xq, TEMP_RANGE_PLUS, TEMP_GEO, 0.0, st)
-            else:
-                H = eng.attend(e32, xq, TEMP_RANGE_PLUS, TEMP_GEO, 1.0, st)
-                G = eng.attend(e32, xq, TEMP_RANGE_PLUS, TEMP_GEO, 0.0, st)
+            kept = eng.kept_queries() == e32.shape[0]      # both passes 2 from the kept logits
+            H, G = (attend_any(eng, kept, 0, e32, xq, TEMP_RANGE_PLUS, TEMP_GEO, b, st) for b in (1.0, 0.0))
             for j, b in enumerate(betas):
                 out[j, i:i + e64.shape[0]] = eng.finalize(eng.blend(G, H, b), e64)
         return out if return_device else self._to_host(out)
@@ -370,7 +390,7 @@ class LocationEncoder(nn.Module):
         return torch.cat(vals), torch.cat(idxs)
 
 
-class ShardedLocationEncoder(nn.Module):
+class ShardedLocationEncoder(_EncoderBase):
     """RANGE / RANGE+ over a bank ROW-SHARDED across the ranks of a ``torch.distributed`` group (one
     process per GPU, backend "nccl" = RCCL over xGMI): ``load_model(..., shards=W)`` in every rank of
     a W-process job.  The reference has no distributed code; the call surface is its
@@ -404,19 +424,8 @@ class ShardedLocationEncoder(nn.Module):
         want = getattr(args, "shards", None)
         if isinstance(want, int) and not isinstance(want, bool) and want != self.world:
             raise ValueError(f"shards={want} but the process group has {self.world} ranks")
-        if self.location_model_name == "RANGE":                          # range.py:102-105
-            self.args.temp = TEMP_RANGE
-            print(f"Using RANGE with temperature {self.args.temp}")
-        elif self.location_model_name == "RANGE+":                       # :107-112
-            self.args.geo_temp = TEMP_GEO
-            self.args.temp = TEMP_RANGE_PLUS
-            print(f"Using RANGE+ with temperatures {self.args.temp} and {self.args.geo_temp}")
-        else:
-            raise ValueError("Unimplemented RANGE model")                 # :113-114
-        bank = load_bank(args.range_db)
-        enc = read_checkpoint(args.pretrained_path)
-        if enc.embed_dim != 256:
-            raise ValueError(f"checkpoint embed_dim {enc.embed_dim} != bank key width 256")
+        self._range_temperatures()
+        bank, enc = _load(args, with_bank=True)
         self.location_feature_dim = 1024 + 256                           # :86
         self.encoder_params = enc
         self.n_bank_rows = bank.n_rows
@@ -427,23 +436,10 @@ class ShardedLocationEncoder(nn.Module):
         if self.n_bank_rows < self.row_shards:
             raise ValueError(f"bank of {self.n_bank_rows} rows cannot be sharded over {self.row_shards} ranks")
         self.row_range = shard_rows(bank.n_rows, self.row_shards, shard_index)
-        self._device = _device_of(args.device)
-        self.engine = make_engine(enc, bank.rows(*self.row_range), self._device, row_offset=self.row_range[0],
-                                  sh_eval=getattr(args, "sh_eval", None), sh_source=getattr(args, "sh_source", None),
-                                  pv_mode=getattr(args, "pv_mode", None))
+        self.engine = self._make_engine(enc, bank.rows(*self.row_range), row_offset=self.row_range[0])
         self.sharded = ShardedRange(self.engine, self.location_model_name, args.beta, group=self.shard_group)
         self.loc_model = SatCLIPLocationModel(self.engine, enc)          # range.py:83-84 (replicated on every rank)
-        self.loc_model.eval()                                            # :201-203
-        for params in self.loc_model.parameters():
-            params.requires_grad = False
-        self.eval()
-
-    def _coords(self, coords) -> torch.Tensor:
-        if not torch.is_tensor(coords):
-            coords = torch.as_tensor(np.asarray(coords))
-        if coords.dim() != 2 or coords.shape[1] != 2:
-            raise ValueError(f"coords must be (B,2) (lon,lat) degrees, got {tuple(coords.shape)}")
-        return coords.to(device=self.engine.device, dtype=torch.float64).contiguous()
+        self._freeze()
 
     def _own_rows(self, B: int):
         return (B * self.rank) // self.world, (B * (self.rank + 1)) // self.world
@@ -453,18 +449,17 @@ class ShardedLocationEncoder(nn.Module):
         all-gather: the row counts differ by at most one).  ``with_flags`` (float64 rows): one more row
         travels with every rank's share, carrying its engine's give-up flag (range_async_error_flag:
         written on the device, in stream order behind the rank's kernels); returns (rows, (W,) flags)."""
-        import torch.distributed as dist
+        from .dist import start_collective
         W = self.world
         per = (B + W - 1) // W
         extra = 1 if with_flags else 0
         send = torch.zeros((per + extra,) + tuple(own.shape[1:]), dtype=own.dtype, device=own.device)
         send[:own.shape[0]] = own
-        if with_flags and hasattr(self.engine, "async_error_flag"):
+        if with_flags:
             self.engine.async_error_flag(out=send[per].view(-1)[0:1])
-        staged = send.is_cuda and dist.get_backend(self.group) == "gloo"
-        src = send.cpu() if staged else send
-        allr = torch.empty((W * (per + extra),) + tuple(own.shape[1:]), dtype=own.dtype, device=src.device)
-        dist.all_gather_into_tensor(allr, src, group=self.group)
+        work, landed = start_collective("all_gather_into_tensor", send, self.group)
+        work.wait()
+        allr = landed()
         parts = []
         for r in range(W):
             n = (B * (r + 1)) // W - (B * r) // W
@@ -480,11 +475,7 @@ class ShardedLocationEncoder(nn.Module):
         top-k from the same call (``LocationEncoder.forward``): the queries are encoded and gathered
         once, the per-shard candidates merge through ONE all-gather (``ShardedRange.forward``)."""
         x = self._coords(coords)
-        k = None
-        if return_topk is not None:
-            k = int(return_topk)
-            if not 1 <= k <= _native.MAX_TOPK:
-                raise ValueError(f"return_topk must be in 1..{_native.MAX_TOPK}, got {return_topk}")
+        k = None if return_topk is None else _topk_arg(return_topk)
         if local:
             res = self.sharded.embed(x, topk=k)
             if not k:

@@ -177,8 +177,7 @@ class ShardedEmbeddingPipeline:
             nb = per * 1280 * 8
             sharded._count("results", 0 if r == 0 else nb, (W - 1) * nb if r == 0 else 0)
             flag, flags, flags_host = self._slots[slot][3:]
-            if hasattr(self.model.engine, "async_error_flag"):
-                self.model.engine.async_error_flag(out=flag)        # (behind this batch's kernels, in stream order)
+            self.model.engine.async_error_flag(out=flag)            # (behind this batch's kernels, in stream order)
             host = None
             if self.staged:
                 h = send.cpu()

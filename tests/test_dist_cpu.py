@@ -137,6 +137,19 @@ class OracleShardEngine:
                 torch.from_numpy(np.take_along_axis(i, order, 1)))
 
 
+def test_both_engines_provide_the_shard_engine_contract():
+    """Every method ``dist.ShardEngine`` names - what ``ShardedRange`` calls - is an attribute of the
+    product's engine CLASS and of the checker above (no GPU, no library): a third engine or a renamed
+    method fails here, at a glance, and not in the middle of a collective."""
+    from range_amd import _native
+    from range_amd.dist import ShardEngine
+    names = sorted(n for n, v in vars(ShardEngine).items() if callable(v) and not n.startswith("_"))
+    assert {"encode", "scan_stats_at", "finalize", "topk_stream"} <= set(names)      # (the listing itself works)
+    for cls in (_native.HipEngine, OracleShardEngine):
+        missing = [n for n in names if not callable(getattr(cls, n, None))]
+        assert not missing, (cls.__name__, missing)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
