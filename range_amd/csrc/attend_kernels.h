@@ -829,6 +829,22 @@ __device__ __forceinline__ void mfma_a(f32x4& acc, float a, float b) {
     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0\n\ts_nop 1" : "+a"(acc) : "v"(a), "v"(b));
 }
 
+// The two scalings of a kept-logit weight (w = ca * e1 + cb * e2) as ONE scalar-float VALU
+// instruction each.  Written as C++, hipcc's SLP vectoriser packs the products of neighbouring rows
+// into v_pk_mul_f32 / v_pk_fma_f32 - and a packed float32 instruction beside MFMAs costs more MFMA
+// issue time than the two scalar ones it replaces.  The packed forms round each
+// lane like these, so the bits are the same.
+__device__ __forceinline__ float valu_mul(float a, float b) {
+    float d;
+    asm volatile("v_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ float valu_fma(float a, float b, float c) {
+    float d;
+    asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+
 // 8 bank rows x 1024 columns of w @ V for this wave's 16 queries, as 16 steps of 8 MFMAs (4
 // accumulator tiles x 2 rows).  Two devices keep the MFMA pipe fed with one wave per SIMD:
 //  * hook(h), h = 0..59, is inlined after every second MFMA: scalar/vector work placed there in
@@ -908,6 +924,52 @@ __device__ __forceinline__ void pv_steps(const float* vslot, float w0, float w1,
 }
 #undef RANGE_PV_MFMA
 
+// A whole 16-row block in ONE phase (pass 2 on kept logits, whose V ring holds whole blocks): steps
+// S = 0..15 go over rows 0-7 with (w[0], w[1]), steps 16..31 over rows 8-15 with (w[2], w[3]); the
+// read pipeline runs through the half boundary, so a block has one hand-over instead of two.  Every
+// accumulator tile sees the same products in the same order as from two pv_steps halves.  s0/s1 =
+// operands of steps 0 and 1; steps 30 and 31 are returned in `carry`; hook(h), h = 0..239, runs
+// after MFMA h (h < 128: first half).
+// (Template recursion, not a loop: 30 steps of 8 hooks are beyond what `#pragma unroll` unrolls in
+// full before the hooks are folded, and a partly unrolled loop evaluates the hooks at run time.)
+template <int S, class Hook>
+__device__ __forceinline__ void pv_block_step(const float* base, const f32x4& w, f32x4& v0, f32x4& v1,
+                                              f32x4& n0, f32x4& n1, f32x4 (&acc)[64], Hook& hook) {
+#define RANGE_PV_MFMA(tile, w, v, h)                 \
+    mfma_a(acc[tile], w, v);                         \
+    __builtin_amdgcn_sched_barrier(0);               \
+    hook(h);                                         \
+    __builtin_amdgcn_sched_barrier(0)
+    if constexpr (S < 30) {
+        // the reads of step S+2 sit in front of step S's 8 MFMAs (512 cycles of cover)
+        constexpr int T = S & 15, S2 = S + 2;
+        const float* src = base + (S2 >> 4) * 8 * VAL_DIM + 64 * (S2 & 15);
+        const f32x4 m0 = *reinterpret_cast<const f32x4*>(src);
+        const f32x4 m1 = *reinterpret_cast<const f32x4*>(src + VAL_DIM);
+        const float w0 = S < 16 ? w[0] : w[2], w1 = S < 16 ? w[1] : w[3];
+        RANGE_PV_MFMA(4 * T + 0, w0, v0.x, 8 * S + 0);
+        RANGE_PV_MFMA(4 * T + 1, w0, v0.y, 8 * S + 1);
+        RANGE_PV_MFMA(4 * T + 2, w0, v0.z, 8 * S + 2);
+        RANGE_PV_MFMA(4 * T + 3, w0, v0.w, 8 * S + 3);
+        RANGE_PV_MFMA(4 * T + 0, w1, v1.x, 8 * S + 4);
+        RANGE_PV_MFMA(4 * T + 1, w1, v1.y, 8 * S + 5);
+        RANGE_PV_MFMA(4 * T + 2, w1, v1.z, 8 * S + 6);
+        RANGE_PV_MFMA(4 * T + 3, w1, v1.w, 8 * S + 7);
+        v0 = n0; v1 = n1; n0 = m0; n1 = m1;
+        pv_block_step<S + 1>(base, w, v0, v1, n0, n1, acc, hook);
+    }
+#undef RANGE_PV_MFMA
+}
+
+template <class Hook>
+__device__ __forceinline__ void pv_block_steps(const float* vslot, const f32x4& w, PvOps s0, PvOps s1,
+                                               f32x4 (&acc)[64], int lane, PvCarry& carry, Hook&& hook) {
+    const float* base = vslot + (2 * (lane >> 4)) * VAL_DIM + 4 * (lane & 15);
+    f32x4 v0 = s0.v0, v1 = s0.v1, n0 = s1.v0, n1 = s1.v1;
+    pv_block_step<0>(base, w, v0, v1, n0, n1, acc, hook);
+    carry.v0a = v0; carry.v1a = v1; carry.v0b = n0; carry.v1b = n1; carry.w0 = w[2]; carry.w1 = w[3];
+}
+
 // MFMA results -> any non-MFMA reader: wait states first (hipcc pads nothing after an asm MFMA).
 __device__ __forceinline__ void acc_fence(f32x4 (&acc)[64]) {
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
@@ -917,6 +979,16 @@ __device__ __forceinline__ void acc_fence(f32x4 (&acc)[64]) {
                           "+a"(acc[i + 4]), "+a"(acc[i + 5]), "+a"(acc[i + 6]), "+a"(acc[i + 7]),
                           "+a"(acc[i + 8]), "+a"(acc[i + 9]), "+a"(acc[i + 10]), "+a"(acc[i + 11]),
                           "+a"(acc[i + 12]), "+a"(acc[i + 13]), "+a"(acc[i + 14]), "+a"(acc[i + 15]));
+}
+
+// In front of carried steps whose weights hipcc may just have copied (v_mov) on the way in from another
+// block: it pads nothing between a VALU write and an asm MFMA that reads the register.
+__device__ __forceinline__ void carry_wait_states() { asm volatile("s_nop 1"); }
+
+// the accumulators as opaque values in the AGPR file (no wait states: not behind an MFMA)
+__device__ __forceinline__ void acc_pin(f32x4 (&acc)[64]) {
+#pragma unroll
+    for (int i = 0; i < 64; ++i) asm volatile("" : "+a"(acc[i]));
 }
 
 // The segments of this workgroup (pass 2): one (split, query tile) item, or the walk of a stream-K
@@ -1187,26 +1259,42 @@ __global__ __launch_bounds__(256, 1) void attend_kernel(ScanArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// pass 2 on KEPT logits.  Same schedule, same V ring, same weight arithmetic and summation order as
-// attend_kernel (the outputs are bit-identical), but the semantic logits of block t+1 are not
+// pass 2 on KEPT logits.  Same weight arithmetic and the same summation order per accumulator tile
+// as attend_kernel (the outputs are bit-identical), but the semantic logits of block t+1 are not
 // recomputed (64 of the 321 MFMAs per block and wave): pass 1 left them in HBM in accumulator
 // order, and they arrive like a K tile did - one 1 KB LDS-DMA per wave and block into a 2-slot
 // ring - at 4 B per (query, row) of extra HBM traffic each way, on a kernel that is MFMA-bound.
 // The geographic tile (one MFMA per block) is still recomputed from the X ring.
-// LDS map (bytes): V ring 3 x 32 KB | S ring 2 x 4 KB (1 KB per wave) | X ring 2 x 256 B
-// LDS-DMA groups: E(t) = 8 V pieces, O(t) = 8 V + 1 S + 1 X = 10.
+//
+// Without a K ring the LDS holds two WHOLE blocks of V, so the waves meet once per block, not once
+// per half, and a block is one phase of 256 + 1 MFMAs (pv_block_steps):
+//   block t : wait(everything)+barrier | first LDS reads: S/X of block t+1, V steps 0-1 of block t
+//             | the 2 carried steps of block t-1 | geo MFMA of block t+1
+//             | PV rows 0-7   (+ issue S/X tile t+2, then the 16 V pieces of block t+1)
+//             | PV rows 8-15  (+ the weights of block t+1, one VALU instruction per gap)
+// V block t lives in ring slot t&1; S/X tile t in slot t&1.  The barrier at the top of block t
+// covers landing (all of a wave's outstanding LDS-DMAs were issued in the FIRST half of block t-1:
+// at least half a block of lead, so the wait is vmcnt(0)) and re-use (every wave has finished
+// reading V block t-1 and S/X tile t, whose slots this block refills; the carried steps hold their
+// operands in registers).  The block loop is unrolled by two, which makes every slot address a
+// constant and w_cur / w_next two names.  Past the segment's last block the prefetches re-read
+// that block (clamped) into slots nobody reads any more: the steady state is branch-free.
+// LDS map (bytes): V ring 2 x 64 KB | S ring 2 x 4 KB (1 KB per wave) | X ring 2 x 256 B = 139,776 B
+// LDS-DMA operations per wave and block: 1 S + 1 X + 16 V = 18.
 // ------------------------------------------------------------------------------------------------
-constexpr int ATTEND_STORED_LDS_BYTES = (3 * 8 * VAL_DIM + 2 * 1024 + 2 * 64) * 4;
+constexpr int ATTEND_STORED_LDS_BYTES = (2 * BLK * VAL_DIM + 2 * 1024 + 2 * 64) * 4;
+
+template <int V> struct IntC { __device__ constexpr operator int() const { return V; } };
 
 template <bool GEO>
 __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* vring = reinterpret_cast<float*>(smem);          // 3 slots x [8][1024]
+    float* vring = reinterpret_cast<float*>(smem);          // 2 slots x [16][1024]
+    constexpr uint32_t VB_BYTES = BLK * VAL_DIM * 4;
     const uint32_t lds0 = (uint32_t)(uintptr_t)RANGE_LPTR(smem);
     const uint32_t vring_lds = lds0;
-    const uint32_t sring_lds = lds0 + 3 * 8 * VAL_DIM * 4;
+    const uint32_t sring_lds = lds0 + 2 * VB_BYTES;
     const uint32_t xring_lds = sring_lds + 2 * 4096;
-    constexpr uint32_t VS_BYTES = 8 * VAL_DIM * 4;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1238,8 +1326,11 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
     f32x4 acc[64];
 #pragma unroll
     for (int i = 0; i < 64; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // (opaque zeros: as plain constants hipcc re-creates them in front of the odd tail, gives the tail
+    // another register assignment than the loop and shuffles - and spills - the tiles between the two)
+    acc_pin(acc);
 
-    const char* sring_b = smem + 3 * 8 * VAL_DIM * 4;
+    const char* sring_b = smem + 2 * VB_BYTES;
     const char* xring_b = sring_b + 2 * 4096;
     const uint32_t s_rd = (uint32_t)(wave * 1024 + lane * 16);                  // this lane's logits
     const uint32_t x_rd = (uint32_t)((pi_row(lane & 15) * 4 + g) * 4);          // as KAddr::x
@@ -1255,15 +1346,21 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
                  sring_lds + slot * 4096 + wave * 1024);
         dma_b32(a.xyz4 + (int64_t)block * BLK * 4, (uint32_t)(lane << 2), xring_lds + slot * 256);
     };
+    // pad rows exist only in the bank's last block, and that can only be a segment's last: their
+    // weights are zeroed once, in front of that block
+    auto zero_pad_rows = [&](f32x4& w, int valid) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = prow[r] < valid ? w[r] : 0.f;
+    };
 
-    f32x4 w_cur = {0.f, 0.f, 0.f, 0.f};
+    f32x4 w_a = {0.f, 0.f, 0.f, 0.f}, w_b = {0.f, 0.f, 0.f, 0.f};
     if (nb > 0) {
         const int64_t r0 = (int64_t)b0 * BLK;
         issue_sx(b0, 0);
         issue_v_half(a.values, r0, vring_lds, wave, lane);
-        issue_v_half(a.values, r0 + 8, vring_lds + VS_BYTES, wave, lane);
+        issue_v_half(a.values, r0 + 8, vring_lds + VB_BYTES / 2, wave, lane);
         issue_sx(nb > 1 ? b0 + 1 : b0, 1);
-        RANGE_WAIT_BARRIER(18);
+        RANGE_WAIT_BARRIER(18);                             // S/X tile 0 has landed
         const f32x4 sv = *reinterpret_cast<const f32x4*>(sring_b + s_rd);
         f32x4 cg = {0.f, 0.f, 0.f, 0.f};
         if (GEO) {
@@ -1275,92 +1372,86 @@ __global__ __launch_bounds__(256, 1) void attend_stored_kernel(ScanArgs a) {
         for (int r = 0; r < 4; ++r) {
             float wr = ca * __builtin_amdgcn_exp2f(fmaf(sv[r], a.k_sem, -m1));
             if (GEO) wr = fmaf(cb, __builtin_amdgcn_exp2f(fmaf(cg[r], a.k_geo, -m2)), wr);
-            w_cur[r] = prow[r] < n_left ? wr : 0.f;
+            w_a[r] = wr;
         }
     }
-    int vs = 0;   // V slot of half 2t
     PvCarry carry;
     carry.v0a = carry.v1a = carry.v0b = carry.v1b = f32x4{0.f, 0.f, 0.f, 0.f};
     carry.w0 = carry.w1 = 0.f;
     const int b_last = b1 - 1;
-    for (int t = 0; t < nb; ++t) {
-        const int vs1 = vs == 2 ? 0 : vs + 1;
-        const int vs2 = vs1 == 2 ? 0 : vs1 + 1;
+
+    // block t of the segment, in ring slot P = t & 1, with the weights w_cur; forms w_next (block t+1)
+    auto run_block = [&](auto par, int t, const f32x4& w_cur, f32x4& w_next) __attribute__((always_inline)) {
+        const int P = par;
         const int bn1 = min(b0 + t + 1, b_last), bn2 = min(b0 + t + 2, b_last);
-        const float* vsrc1 = a.values + ((int64_t)bn1 * BLK + 2 * wave) * VAL_DIM;     // rows 2w, 2w+1
+        const float* vsrc1 = a.values + ((int64_t)bn1 * BLK + 2 * wave) * VAL_DIM;     // rows 2w, 2w+1 (+8)
         const float* ssrc2 = a.logits + logit_tile(qtile_kept, a.n_blocks, bn2, wave);
         const float* xsrc2 = a.xyz4 + (int64_t)bn2 * BLK * 4;
-        const uint32_t vdst_e = vring_lds + vs2 * VS_BYTES + wave * 8192;   // half 2t+2
-        const uint32_t vdst_o = vring_lds + vs * VS_BYTES + wave * 8192;    // half 2t+3
-        const uint32_t sdst = sring_lds + (t & 1) * 4096 + wave * 1024;
-        const uint32_t xdst = xring_lds + (t & 1) * 256;
-        // ---- half 2t : leaves O(t-1) = 10 operations in flight
-        RANGE_WAIT_BARRIER(10);
-        {
-            PvOps s0, s1;
-            pv_first_reads(vring + vs * 8 * VAL_DIM, lane, s0, s1);
-            pv_exec_carry(acc, carry);                       // last step of the previous half
-            pv_steps(vring + vs * 8 * VAL_DIM, w_cur[0], w_cur[1], s0, s1, acc, lane, carry,
-                     [&](int h) __attribute__((always_inline)) {
-                         if (h % 14 == 3) {                  // 8 pieces: V half 2t+2
-                             const int ii = h / 14;
-                             if ((ii & 3) == 0) dma_group_begin(vdst_e + (ii >> 2) * 4096);
-                             dma_b128_q(vsrc1 + (ii >> 2) * VAL_DIM, vvoff, ii & 3);
-                         }
-                     });
-        }
-        // ---- half 2t+1 : leaves E(t) = 8 operations in flight
-        RANGE_WAIT_BARRIER(8);
+        const uint32_t vdst = vring_lds + (P ^ 1) * VB_BYTES + wave * 8192;     // block t+1
+        const uint32_t sdst = sring_lds + P * 4096 + wave * 1024;               // tile t+2
+        const uint32_t xdst = xring_lds + P * 256;
+        const float* vslot = vring + P * BLK * VAL_DIM;
+        RANGE_WAIT_BARRIER(0);
         PvOps s0, s1;
         f32x4 cg = {0.f, 0.f, 0.f, 0.f};
-        const f32x4 sv = *reinterpret_cast<const f32x4*>(sring_b + ((t + 1) & 1) * 4096 + s_rd);
+        const f32x4 sv = *reinterpret_cast<const f32x4*>(sring_b + (P ^ 1) * 4096 + s_rd);
         {
-            const float xa = GEO ? *reinterpret_cast<const float*>(xring_b + ((t + 1) & 1) * 256 + x_rd) : 0.f;
-            pv_first_reads(vring + vs1 * 8 * VAL_DIM, lane, s0, s1);
-            pv_exec_carry(acc, carry);                       // last step of half 2t
+            const float xa = GEO ? *reinterpret_cast<const float*>(xring_b + (P ^ 1) * 256 + x_rd) : 0.f;
+            pv_first_reads(vslot, lane, s0, s1);
+            carry_wait_states();
+            pv_exec_carry(acc, carry);                       // last 2 steps of block t-1
             if (GEO) mfma_v_first(cg, xa, fxq);
         }
-        f32x4 w_next = {0.f, 0.f, 0.f, 0.f};
         float e1[4], e2[4];
-        const int n_left1 = n_left - (t + 1) * BLK;
-        pv_steps(vring + vs1 * 8 * VAL_DIM, w_cur[2], w_cur[3], s0, s1, acc, lane, carry,
+        pv_block_steps(vslot, w_cur, s0, s1, acc, lane, carry,
                 [&](int h) __attribute__((always_inline)) {
-                    if ((h & 7) == 3) {
-                        const int ii = h >> 3;               // 10 pieces: V half 2t+3, S/X tile t+2
-                        if (ii < 8) {
-                            if ((ii & 3) == 0) dma_group_begin(vdst_o + (ii >> 2) * 4096);
-                            dma_b128_q(vsrc1 + (8 + (ii >> 2)) * VAL_DIM, vvoff, ii & 3);
-                        } else if (ii == 8) {
-                            dma_b128(ssrc2, vvoff, sdst);
-                        } else if (ii == 9) {
-                            dma_b32(xsrc2, (uint32_t)(lane << 2), xdst);
+                    if (h < 128) {
+                        if (h % 6 == 3) {                    // 18 pieces: S/X tile t+2, V block t+1
+                            const int ii = h / 6;
+                            if (ii == 0) {
+                                dma_b128(ssrc2, vvoff, sdst);
+                            } else if (ii == 1) {
+                                dma_b32(xsrc2, (uint32_t)(lane << 2), xdst);
+                            } else if (ii < 18) {
+                                const int p = ii - 2, hh = p >> 3, row = (p >> 2) & 1, qq = p & 3;
+                                if (qq == 0) dma_group_begin(vdst + hh * (VB_BYTES / 2) + row * 4096);
+                                dma_b128_q(vsrc1 + (8 * hh + row) * VAL_DIM, vvoff, qq);
+                            }
                         }
-                    } else if (h >= 22 && h < 78 && (h & 1) == 0) {
+                    } else if (h >= 150 && h < 206 && (h & 1) == 0) {
                         // weights of block t+1, ONE VALU instruction per MFMA gap (an exp2 is a
-                        // quarter-rate instruction: two of them in one gap delay the next MFMA);
-                        // even h only, the LDS-DMA pieces sit on odd h.  The first runs > 20
-                        // MFMAs after the geo MFMA, whose result is long readable.
-                        const int k = (h - 22) >> 1, r = k / 7, op = k % 7;
+                        // quarter-rate instruction: two of them in one gap delay the next MFMA).
+                        // The first runs > 140 MFMAs after the geo MFMA, whose result is long
+                        // readable.
+                        const int k = (h - 150) >> 1, r = k / 7, op = k % 7;
                         if (op == 0) e1[r] = fmaf(sv[r], a.k_sem, -m1);
                         else if (op == 1) { if (GEO) e2[r] = fmaf(cg[r], a.k_geo, -m2); }
                         else if (op == 2) e1[r] = __builtin_amdgcn_exp2f(e1[r]);
                         else if (op == 3) { if (GEO) e2[r] = __builtin_amdgcn_exp2f(e2[r]); }
-                        else if (op == 4) e1[r] = ca * e1[r];
-                        else if (op == 5) { if (GEO) e1[r] = fmaf(cb, e2[r], e1[r]); }
+                        else if (op == 4) e1[r] = valu_mul(ca, e1[r]);
+                        else if (op == 5) { if (GEO) e1[r] = valu_fma(cb, e2[r], e1[r]); }
                         else w_next[r] = e1[r];
                     }
                 });
-        // pad rows exist only in the bank's last block: their weights are zeroed here, outside
-        // the MFMA gaps (a VALU instruction in a gap costs MFMA issue time)
-        if (n_left1 < BLK) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) w_next[r] = prow[r] < n_left1 ? w_next[r] : 0.f;
+    };
+
+    if (nb > 0) {
+        // the segment's last block is the only one that can hold pad rows
+        const int valid_last = n_left - (nb - 1) * BLK;
+        int t = 0;
+        for (; t + 2 <= nb; t += 2) {
+            run_block(IntC<0>{}, t, w_a, w_b);
+            if (t + 2 == nb && valid_last < BLK) zero_pad_rows(w_b, valid_last);
+            run_block(IntC<1>{}, t + 1, w_b, w_a);
         }
-        w_cur = w_next;
-        vs = vs2;
+        if (t < nb) {                                        // odd tail
+            if (valid_last < BLK) zero_pad_rows(w_a, valid_last);
+            run_block(IntC<0>{}, t, w_a, w_b);
+        }
+        carry_wait_states();
+        pv_exec_carry(acc, carry);                           // last 2 steps of the last block
     }
-    if (nb > 0) pv_exec_carry(acc, carry);   // last step of the last half
-    // the clamped prefetches of the last iterations are still in flight into this workgroup's LDS
+    // the clamped prefetches of the last blocks are still in flight into this workgroup's LDS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     acc_fence(acc);
