@@ -17,7 +17,7 @@
 //   byte address ((((R*4 + P)*16 + ct)*3 + p)*64 + lane)*16
 // so a B operand is one coalesced 1 KB load per wave.  Element i of lane (n, g) is row
 // 32R + (i < 4 ? pi_row(4g+i) : 16 + pi_row(4g+i-4)) - the order in which a lane of pass 1 holds
-// its logits (attend_kernels.h: pi_row) - and column 64*(t>>2) + 4n + (t&3) of tile t = 16P + ct.
+// its logits (engine_prims.h: pi_row) - and column 64*(t>>2) + 4n + (t&3) of tile t = 16P + ct.
 // The weights come straight from the lane's own kept logits.
 //
 // Work decomposition: workgroup = 4 waves = 64 queries; wave w owns the 256 COLUMNS of piece w for
@@ -33,7 +33,9 @@
 // every wave read every piece from LDS (128 B/clk of operand reads next to the DMA writes); with
 // a quarter of those reads (timing experiment) it took 7.0 ms.  This tiling: 7.9 ms.
 #pragma once
-#include "attend_kernels.h"
+#include "engine_prims.h"
+#include "scan_common.h"
+#include "pass2.h"
 
 namespace range_hip {
 
@@ -124,29 +126,21 @@ __global__ __launch_bounds__(256, 1) void attend_bf16x3_kernel(ScanArgs a, const
     const int g = lane >> 4;
     int split, qt;
     decode_block(a, split, qt);
-    const int g0 = (int)(((int64_t)split * n_groups) / a.n_splits);
-    const int g1 = (int)(((int64_t)(split + 1) * n_groups) / a.n_splits);
+    const int g0 = part_begin(split, n_groups, a.n_splits);
+    const int g1 = part_begin(split + 1, n_groups, a.n_splits);
     const int nG = g1 - g0;
     const int64_t q = (int64_t)qt * QTILE + wave * 16 + (lane & 15);
     const int64_t qtile_kept = (int64_t)qt + a.qt_offset;
 
-    float ca, cb, m1, m2, fxq;
-    {
-        const int64_t qq = q < a.B ? q : a.B - 1;
-        const f32x4 st = *reinterpret_cast<const f32x4*>(a.stats + qq * 4);
-        m1 = st.x; m2 = st.z;
-        ca = a.beta / st.y;
-        cb = GEO ? (1.0f - a.beta) / st.w : 0.f;
-        fxq = a.xq[qq * 4 + g];
-    }
-    // (ordinary loads: put hipcc's wait for them in front of the loop, see pin_qfrag)
-    asm volatile("" : "+v"(ca), "+v"(cb), "+v"(m1), "+v"(m2), "+v"(fxq));
+    WeightConsts wc = load_weight_consts<GEO>(a, q);
+    pin_weight_consts(wc);
+    float fxq = a.xq[(q < a.B ? q : a.B - 1) * 4 + g];
+    asm volatile("" : "+v"(fxq));                            // (an ordinary load too: same pin)
     f32x4 acc[64];                 // [query tile m][column tile ct] at 16 m + ct
 #pragma unroll
     for (int i = 0; i < 64; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     int prow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) prow[r] = pi_row(4 * g + r);
+    lane_rows(prow, g);
     const int b_last = a.n_blocks - 1;
     const int xrow = pi_row(lane & 15) * 4 + g;
 
@@ -200,13 +194,8 @@ __global__ __launch_bounds__(256, 1) void attend_bf16x3_kernel(ScanArgs a, const
             asm volatile("s_nop 15" : "+v"(cg));
         }
         const int n_left = (int)(a.n_valid - (int64_t)b * BLK);
-        float w[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float wr = ca * __builtin_amdgcn_exp2f(fmaf(sv[r], a.k_sem, -m1));
-            if (GEO) wr = fmaf(cb, __builtin_amdgcn_exp2f(fmaf(cg[r], a.k_geo, -m2)), wr);
-            w[r] = prow[r] < n_left ? wr : 0.f;
-        }
+        f32x4 w = block_weights<GEO>(wc, a, sv, cg);
+        zero_pad_rows(w, prow, n_left);
         split3(w[0], w[1], h[0], m[0], l[0]);
         split3(w[2], w[3], h[1], m[1], l[1]);
     };
@@ -269,12 +258,12 @@ __global__ __launch_bounds__(256, 1) void attend_bf16x3_kernel(ScanArgs a, const
             const float xa = half ? xaB : xaA;
             const int n_left = (int)(a.n_valid - (int64_t)(bn + half) * BLK);
             if (k == 0) { if (GEO) mfma_v_first(cg, xa, fxq); }
-            else if (k >= 1 && k < 5) e1[k - 1] = fmaf(sv[k - 1], a.k_sem, -m1);
+            else if (k >= 1 && k < 5) e1[k - 1] = fmaf(sv[k - 1], a.k_sem, -wc.m1);
             else if (k >= 5 && k < 9) e1[k - 5] = __builtin_amdgcn_exp2f(e1[k - 5]);
-            else if (k >= 10 && k < 14) { if (GEO) e2[k - 10] = fmaf(cg[k - 10], a.k_geo, -m2); }
+            else if (k >= 10 && k < 14) { if (GEO) e2[k - 10] = fmaf(cg[k - 10], a.k_geo, -wc.m2); }
             else if (k >= 14 && k < 18) { if (GEO) e2[k - 14] = __builtin_amdgcn_exp2f(e2[k - 14]); }
-            else if (k >= 18 && k < 22) ww[k - 18] = ca * e1[k - 18];
-            else if (k >= 22 && k < 26) { if (GEO) ww[k - 22] = fmaf(cb, e2[k - 22], ww[k - 22]); }
+            else if (k >= 18 && k < 22) ww[k - 18] = wc.ca * e1[k - 18];
+            else if (k >= 22 && k < 26) { if (GEO) ww[k - 22] = fmaf(wc.cb, e2[k - 22], ww[k - 22]); }
             else if (k == 26) {
                 if (n_left < BLK) {              // pad rows exist only in the bank's last block
 #pragma unroll

@@ -1,13 +1,13 @@
 // The whole retrieval of a SMALL batch (up to 32 queries) in ONE pass over the bank.
 //
-// The two-pass kernels of attend_kernels.h are built for the FP32-MFMA-bound regime (64 queries per
+// The two-pass kernels of pass1.h / pass2.h are built for the FP32-MFMA-bound regime (64 queries per
 // workgroup, hundreds of workgroups per bank pass).  A handful of queries is the opposite regime:
 // the 513 MB of the bank (keys, locations, values: range/range.py:85-95) are what costs, and two
 // passes over the keys plus a pass over the values with one busy wave per CU took 0.15 ms for 16
 // queries.  Here every CU streams its share of the bank ONCE:
 //
 //   * no softmax statistics are needed in advance: the logits of unit vectors are bounded, the
-//     exponent shift is the constant m = tau * log2(e) (attend_kernels.h, pass 1), so a workgroup
+//     exponent shift is the constant m = tau * log2(e) (pass1.h), so a workgroup
 //     accumulates the UN-NORMALISED products  O_h = sum_n 2^(t_n - m) V_n  and  Z_h = sum_n 2^(t_n - m)
 //     of both heads (h = semantic, geographic: range.py:213-217, :231-236) over its rows, and
 //     small_finalize_kernel sums the workgroups' partials in a fixed order, divides and blends
@@ -41,7 +41,8 @@
 // permutation pi_row, as everywhere: accumulator registers 0,1 of the logit tile are rows of the
 // block's first half, 2,3 of the second, and are directly the A operand of the P @ V MFMAs.
 #pragma once
-#include "attend_kernels.h"
+#include "engine_prims.h"
+#include "scan_common.h"
 
 namespace range_hip {
 
@@ -161,8 +162,7 @@ __global__ __launch_bounds__(256, 1) void attend_small_kernel(SmallArgs a) {
     // B fragment of P @ V, lane (n = j, kg = g): V row 2 g + (r & 1) of the half, this lane's 4 columns
     const uint32_t voff_r0 = (uint32_t)((2 * g) * 1024 + (j << 4));
     uint32_t prow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) prow[r] = (uint32_t)pi_row(4 * g + r);
+    lane_rows(prow, g);
 
     f32x4 acc[NQ][2][16];
     float z1[NQ], z2[NQ];

@@ -37,7 +37,7 @@ inline int choose_splits(int n_qtiles, int n_blocks, int n_cu, int wg_per_cu, in
     return best;
 }
 
-// Stream-K partition of pass 2 (attend_kernels.h: SlabMap / SegWalk; round 5): U units in order are cut
+// Stream-K partition of pass 2 (scan_common.h: SlabMap, pass2.h: SegWalk; round 5): U units in order are cut
 // into G contiguous, near-equal ranges [start(w), start(w + 1)); owner(u) is the range a unit falls in.
 // The kernel walks by `start`, the reduction finds a query tile's parts by `owner`: both are these
 // functions (compiled for the device too: RANGE_HD), and tests/native/host_sanitize.cpp checks that they
@@ -51,8 +51,10 @@ inline int choose_splits(int n_qtiles, int n_blocks, int n_cu, int wg_per_cu, in
 #endif
 RANGE_HD int64_t sk_start(int64_t w, int64_t U, int64_t G) { return (w * U) / G; }
 RANGE_HD int64_t sk_owner(int64_t u, int64_t U, int64_t G) { return ((u + 1) * G - 1) / U; }
-// first block of bank column c of n_cols (columns: contiguous, near-equal block ranges)
-RANGE_HD int sk_col_begin(int c, int n_blocks, int n_cols) { return (int)(((int64_t)c * n_blocks) / n_cols); }
+// first of n items that part i of n_parts takes (parts: contiguous, near-equal ranges; part i ends where
+// part i + 1 begins): the bank blocks of a split, a chunk, a stream-K column or a workgroup
+RANGE_HD int part_begin(int i, int n, int n_parts) { return (int)(((int64_t)i * n) / n_parts); }
+RANGE_HD int sk_col_begin(int c, int n_blocks, int n_cols) { return part_begin(c, n_blocks, n_cols); }   // first block of bank column c
 
 // Small-batch encoder: workgroups per 16-query tile = column parts S (a power of two, parts of
 // 64 .. 512 columns: the widths a kernel exists for) x K parts KP (ranges of at least 3 of the
@@ -221,7 +223,7 @@ inline std::vector<double> pack_weights(const double* W, int n_out, int k_in, co
 // Integer constants of the kernel headers that the plans need.  The kernel headers keep the only
 // definition of each; range_hip.hip fills this struct from them once (PLAN_CONSTS).
 struct PlanConsts {
-    int qtile, blk, val_dim, max_topk, p1_wg_per_cu;   // attend_kernels.h: QTILE, BLK, VAL_DIM, MAX_TOPK, P1_WG_PER_CU
+    int qtile, blk, val_dim, max_topk, p1_wg_per_cu;   // engine_prims.h: QTILE, BLK, VAL_DIM, MAX_TOPK; pass1.h: P1_WG_PER_CU
     int enc_qtile;                                     // encoder_kernel.h: ENC_QTILE
     int topks_wl;                                      // topk_stream.h: TOPKS_WL
     int tg_qblock, tg_wg_per_cu, tg_cap_l;             // topk_gemm.h: TG_QBLOCK, TG_WG_PER_CU, TG_CAP_L
@@ -434,7 +436,7 @@ inline Pass2Plan plan_pass2(int n_cu, int64_t n_rows, int64_t B, bool allow_stre
     p.n_splits = choose_splits(p.n_qtiles, p.n_blocks, n_cu, 1,
                                std::max(32, std::min(512, (n_cu + p.n_qtiles - 1) / p.n_qtiles)),
                                std::max(0.001, 140.0 / (double)n_rows));
-    // Stream-K (attend_kernels.h: SlabMap): as many workgroups as CUs, each with the same number of
+    // Stream-K (scan_common.h: SlabMap): as many workgroups as CUs, each with the same number of
     // (query tile, bank block) units (at least 4: tiny launches take fewer workgroups), one slab per
     // query tile a workgroup touches.  For banks and SHARDS of up to 50 000 rows - measured, 10 000
     // queries, pass 2 + its reduction, against one workgroup per (split, query tile): 12 500 rows (a

@@ -16,7 +16,10 @@
 #include "host_common.h"
 #include "host_copy.h"
 #include "host_plan.h"
-#include "attend_kernels.h"
+#include "scan_common.h"
+#include "topk_lists.h"
+#include "pass1.h"
+#include "pass2.h"
 #include "topk_stream.h"
 #include "topk_gemm.h"
 #include "attend_bf16x3.h"
@@ -101,7 +104,7 @@ struct range_ctx {
         int last_qtiles = 0, last_splits = 0;    // range_last_attend_geometry
     } pass;
     // logits kept by the last range_scan_stats(keep_logits = 1): kept_B queries x kept_blocks
-    // bank blocks, 1 KB tiles (attend_kernels.h: logit_tile); kept_B == 0: nothing kept
+    // bank blocks, 1 KB tiles (scan_common.h: logit_tile); kept_B == 0: nothing kept
     struct Kept {
         DevBuf<float> ws_logits, ws_rowmax, ws_theta;
         int64_t kept_B = 0, kept_total = 0;

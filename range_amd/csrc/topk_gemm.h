@@ -204,8 +204,8 @@ __global__ __launch_bounds__(TG_WAVES * 64, 2) void topk_gemm_kernel(TopkGemmArg
     // consecutive workgroups take the query blocks of ONE split: its key tiles are shared in L2
     const int split = (int)blockIdx.x / a.n_qblocks, qb = (int)blockIdx.x - split * a.n_qblocks;
     // the split's tiles, or (pass A) every tile_stride-th of them: "tile" counts the visited ones
-    const int t0 = (int)(((int64_t)split * a.n_blocks) / a.n_splits);
-    const int t1 = (int)(((int64_t)(split + 1) * a.n_blocks) / a.n_splits);
+    const int t0 = part_begin(split, a.n_blocks, a.n_splits);
+    const int t1 = part_begin(split + 1, a.n_blocks, a.n_splits);
     const int stride = a.tile_stride;
     const int b0 = 0, b1 = (t1 - t0 + stride - 1) / stride;
     const int n_phase = (b1 - b0 + TG_KT - 1) / TG_KT;
@@ -265,8 +265,7 @@ __global__ __launch_bounds__(TG_WAVES * 64, 2) void topk_gemm_kernel(TopkGemmArg
     issue(1);
 
     uint32_t prow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) prow[r] = (uint32_t)pi_row(4 * g + r);
+    lane_rows(prow, g);
     const uint32_t n_valid32 = (uint32_t)a.n_valid;
     // byte offset of this lane's candidate list per group (the host keeps all lists below 4 GB)
     uint32_t list_off[TG_GQ];

@@ -36,10 +36,12 @@
 //   launch (topk_merge_kernel).
 //
 // Dot products are the same single dependent MFMA chain, in the same k order, as in the scan
-// kernels of attend_kernels.h: every kernel that forms a similarity gets the same float.
+// kernels of scan_common.h (qk_mfma): every kernel that forms a similarity gets the same float.
 #pragma once
 #include "async_err.h"
-#include "attend_kernels.h"
+#include "engine_prims.h"
+#include "scan_common.h"
+#include "topk_lists.h"
 
 namespace range_hip {
 
@@ -433,8 +435,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void topk_stream_kernel(TopkStream
     KAddr kaddr;
     kaddr.init(lane);
     uint32_t prow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) prow[r] = (uint32_t)pi_row(4 * g + r);
+    lane_rows(prow, g);
     const uint32_t n_valid32 = (uint32_t)a.n_valid;
 
     int k = 0;                                                 // position in the tile sequence
@@ -656,8 +657,7 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
     for (int d = 0; d < DEPTH; ++d) issue_seq(d);
 
     uint32_t prow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) prow[r] = (uint32_t)pi_row(4 * g + r);
+    lane_rows(prow, g);
     const uint32_t n_valid32 = (uint32_t)a.n_valid;
 
     int k = 0;

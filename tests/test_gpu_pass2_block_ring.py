@@ -1,7 +1,12 @@
 """Pass 2 on kept logits with the block-granular V ring (`-m gpu`): ``attend_kept`` (attend_stored_kernel:
 two ring slots of a whole 16-row block, one barrier per block, the block loop unrolled by two with an
-odd tail) bit for bit against ``attend`` (attend_kernel: the recompute kernel on the half-block ring,
-which shares none of the new code), and against the float64 oracle.
+odd tail) bit for bit against ``attend`` (attend_kernel: the recompute kernel), and against the float64
+oracle.  The two kernels share the PV step, the block weights and the write-out (pass2.h: pv_step,
+block_weights, store_acc_tile), so the bitwise comparison does not separate those; it separates what each
+kernel has of its own: a ring of three half blocks against one of two whole blocks, two barriers and
+hand-overs per block against one, pad rows masked in every block against zeroed once in front of the
+last, recomputed against kept logits.  What anchors both, shared code included, is the float64 oracle at
+2e-5.
 
 Bank sizes are the smallest at which the ring, the tail and the segments can go wrong: 16 / 32 / 48 rows
 = 1 / 2 / 3 blocks (the odd tail alone; one unrolled body; body + tail), 53 rows (a last block with 5

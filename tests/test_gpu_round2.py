@@ -215,7 +215,7 @@ def test_topk_stream_drop_seen_by_every_merge_level(level):
         u /= np.linalg.norm(u)
         keys[row] = (s * q[b] + np.sqrt(1 - s * s) * u).astype(np.float32)
 
-    # rows of a 16-row tile held by lane group g (attend_kernels.h: pi_row): g=0 {0,1,8,9}, g=1 {2,3,10,11},
+    # rows of a 16-row tile held by lane group g (engine_prims.h: pi_row): g=0 {0,1,8,9}, g=1 {2,3,10,11},
     # g=2 {4,5,12,13}, g=3 {6,7,14,15}; wave w of workgroup 0 streams tile w * 256 first (256 workgroups)
     if level == "lanes":
         spots = [(0, 16 * 7 + r) for r in (4, 5, 12, 6, 7)]                      # tile 7: lanes g=2 (3 rows), g=3 (2)

@@ -153,19 +153,15 @@ def test_engine_requires_gpu():
         _native.HipEngine("cpu")
 
 
-def test_no_foreign_m0_writes(tmp_path):
-    """The LDS-DMA groups in attend_kernels.h set M0 in one asm statement and rely on it in the
+def test_no_foreign_m0_writes():
+    """The LDS-DMA groups in engine_prims.h set M0 in one asm statement and rely on it in the
     next three (include comment at dma_group_begin).  That is only sound while hipcc itself never
     writes M0 in those kernels: check the generated gfx950 assembly."""
-    import shutil
-    import subprocess
-    if shutil.which("hipcc") is None:
+    from device_asm import device_asm     # (tests/device_asm.py: one compile for all codegen tests)
+    out = device_asm()
+    if out is None:
         pytest.skip("hipcc not available")
-    out = tmp_path / "dev.s"
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S",
-                    "-o", str(out), os.path.join(REPO, "range_amd", "csrc", "range_hip.hip")],
-                   check=True, cwd=REPO, capture_output=True)
-    text = out.read_text()
+    text = open(out).read()
     kernels = re.split(r"\n(?=_ZN9range_hip\w+:)", text)
     checked = 0
     for k in kernels:
@@ -183,7 +179,7 @@ def test_no_foreign_m0_writes(tmp_path):
                 raise AssertionError(f"{name}: compiler-generated M0 access: {line.strip()}")
     assert checked >= 6
     # second check on the same assembly: no instruction right behind an inline-asm MFMA writes one
-    # of its source registers (WAR hazard measured on gfx950, see attend_kernels.h mfma_v)
+    # of its source registers (WAR hazard measured on gfx950, see engine_prims.h mfma_v)
     import importlib.util
     spec = importlib.util.spec_from_file_location("check_mfma_war", os.path.join(REPO, "tools", "check_mfma_war.py"))
     mod = importlib.util.module_from_spec(spec)

@@ -1,0 +1,86 @@
+"""Compare two device assembly listings of the same translation unit, kernel by kernel (CPU only).
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S range_amd/csrc/range_hip.hip -o X.s
+    python tools/kernel_asm_diff.py PARENT.s BRANCH.s
+
+For a refactor that must not change the generated code.  Per kernel symbol: identical or not, and for
+those that differ NumVgprs / NumAgprs / ScratchSize / Occupancy of both sides and, for the innermost
+backward-branch region that holds an MFMA, the instruction counts, whether the register-masked
+instruction sequence is equal and whether the opcode multiset is equal.  Exit status 1 if the symbol
+sets differ, or if ScratchSize, NumAgprs or Occupancy differ anywhere.  It compares what is there; it
+looks for no particular instruction.
+"""
+import collections
+import re
+import sys
+
+FIELDS = ("NumVgprs", "NumAgprs", "ScratchSize", "Occupancy")
+
+
+def innermost_mfma_loop(body):
+    """Lines of the shortest backward-branch region of ``body`` that contains an MFMA."""
+    labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"(\.LBB\d+_\d+):", l)] if m}
+    best = None
+    for i, l in enumerate(body):
+        m = re.match(r"\s+s_c?branch\S*\s+(\.LBB\d+_\d+)", l)
+        if m and labels.get(m.group(1), i) < i:
+            region = body[labels[m.group(1)]:i + 1]
+            if any(re.match(r"\s+v_mfma", r) for r in region) and (best is None or len(region) < len(best)):
+                best = region
+    return best
+
+
+def kernels(text):
+    """{symbol: text from its label to the next global label} for every kernel of a listing."""
+    chunks = re.split(r"\n(?=[A-Za-z_][\w$.]*:)", text)
+    return {c.split(":", 1)[0]: c for c in chunks if re.search(r"^\s*\.amdhsa_kernel\s", c, re.M)}
+
+
+def instructions(lines):
+    """Instructions of a region without comments, labels and directives."""
+    code = (l.split(";")[0].strip() for l in lines)
+    return [c for c in code if c and not c.endswith(":") and not c.startswith((".", "#"))]
+
+
+def masked(code):
+    """Register numbers and local labels replaced: what is left is opcodes, operand kinds, immediates."""
+    return [re.sub(r"\.LBB\d+_\d+", "L", re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1#", c)) for c in code]
+
+
+def main(argv):
+    if len(argv) != 3:
+        print(__doc__)
+        return 2
+    a, b = (kernels(open(p).read()) for p in argv[1:])
+    status = 0
+    for name in sorted(set(a) ^ set(b)):
+        print(f"only in {'parent' if name in a else 'branch'}: {name}")
+        status = 1
+    n_same = 0
+    for name in sorted(set(a) & set(b)):
+        if a[name] == b[name]:
+            n_same += 1
+            continue
+        print(f"differs: {name}")
+        for f in FIELDS:
+            va, vb = (re.search(rf"; {f}: (\d+)", k) for k in (a[name], b[name]))
+            va, vb = (int(v.group(1)) if v else None for v in (va, vb))
+            flag = ""
+            if va != vb and f != "NumVgprs":
+                flag, status = "   <-- must be equal", 1
+            print(f"    {f:12s} {va} -> {vb}{flag}")
+        la, lb = (innermost_mfma_loop(k.splitlines()) for k in (a[name], b[name]))
+        if la is None or lb is None:
+            print(f"    inner MFMA loop: {'none' if la is None and lb is None else 'on one side only'}")
+            continue
+        ca, cb = instructions(la), instructions(lb)
+        ops = lambda code: collections.Counter(c.split()[0] for c in code)
+        print(f"    inner MFMA loop: {len(ca)} -> {len(cb)} instructions; register-masked sequence "
+              f"{'equal' if masked(ca) == masked(cb) else 'DIFFERS'}; opcode multiset "
+              f"{'equal' if ops(ca) == ops(cb) else 'DIFFERS'}")
+    print(f"{len(a)} / {len(b)} kernel symbols, {n_same} identical; exit status {status}")
+    return status
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
