@@ -34,7 +34,8 @@ extern "C" {
 #define RANGE_KEY_DIM 256   /* satclip_embeddings width, range/range.py:85-86 */
 #define RANGE_VAL_DIM 1024  /* image_embeddings width,   range/range.py:86, 90 */
 #define RANGE_OUT_DIM 1280  /* location_feature_dim,     range/range.py:86     */
-#define RANGE_MAX_TAU 43.0f /* largest temperature (the reference's: 12, 15, 40; range.py:103-109) */
+#define RANGE_MAX_TAU 43.0f /* largest temperature of the constant-shift kernels (the reference's defaults: 12, 15, 40; range.py:103-109) */
+#define RANGE_MAX_TAU_SHARP 1000.0f /* largest temperature at all: above RANGE_MAX_TAU pass 1 keeps a running maximum */
 
 enum {
     RANGE_OK = 0,
@@ -180,15 +181,20 @@ int range_coord_features(range_ctx* ctx, int32_t mode, const double* lonlat_dev,
  *   tau_sem, tau_geo : temperatures (range.py:103, 108-109); tau_geo <= 0 disables the geo head
  *   ehat32_dev / xq32_dev rows must be UNIT vectors (what range_encode emits; range.py:212,
  *               utils.py:11-16) and the bank keys / xyz are (range.py:85-89, :93-95): every logit
- *               is then <= 1 and the statistics use the constant shift m = tau*log2(e) instead of
- *               a running maximum (no rescaling; partial statistics merge by plain sums).
- *               Temperatures above RANGE_MAX_TAU are rejected (2^(-2m) must stay a normal float),
+ *               is then <= 1 and, with both temperatures <= RANGE_MAX_TAU, the statistics use the
+ *               constant shift m = tau*log2(e) instead of a running maximum (no rescaling; 2^(-2m)
+ *               stays a normal float).  With either temperature above RANGE_MAX_TAU (up to
+ *               RANGE_MAX_TAU_SHARP) pass 1 keeps a running maximum for both heads
+ *               (sharp_scan_stats_kernel): m is then the largest scaled logit the rows held.
+ *               Temperatures that are not finite, not > 0 or above RANGE_MAX_TAU_SHARP are rejected,
  *               and so is a bank whose largest key or location row norm exceeds 1.001
  *               (RANGE_ERR_INVALID: the constant shift would overflow).
- *   stats_dev : (B,4) float32 = {m_sem, l_sem, m_geo, l_geo}, m = tau*log2(e),
+ *   stats_dev : (B,4) float32 = {m_sem, l_sem, m_geo, l_geo}, m = tau*log2(e) or, above
+ *               RANGE_MAX_TAU, the largest tau*log2(e)*logit;
  *               l = sum 2^(tau*log2(e)*logit - m) over the rows; log-sum-exp = (m + log2 l)/log2 e.
- *               Statistics of disjoint row sets (bank splits, bank shards) of the same query
- *               have the same m and their l add: range_merge_stats, or an all-reduce(sum).
+ *               Statistics of disjoint row sets (bank splits, bank shards) of the same query merge
+ *               exactly whatever their m (range_merge_stats); with the constant shift the m are
+ *               equal and the l add.
  *   topk : 0, or k in [1,16]: also emit the k largest semantic similarities of each query
  *          (the "brute-force top-k" side channel), descending, ties -> lower row index:
  *          topk_val_dev (B,k) float32, topk_idx_dev (B,k) int64 (global row = row_offset + local).
@@ -337,6 +343,13 @@ int range_finalize(range_ctx* ctx, const float* partials_dev, int32_t n_parts,
  *   out_dev : (B,1280) float64 */
 int range_forward(range_ctx* ctx, const double* lonlat_dev, int64_t B, int32_t model, float beta,
                   double* out_dev, range_stream_t stream);
+
+/* The temperatures range_forward / range_forward_host run at, instead of the model's defaults (the
+ * reference reads args.temp / args.geo_temp at call time: range/range.py:215, :234).  0 = the
+ * model's default; tau_geo applies to RANGE_MODEL_RANGE_PLUS only.  Otherwise finite, > 0 and
+ * <= RANGE_MAX_TAU_SHARP (RANGE_ERR_INVALID).  Above RANGE_MAX_TAU every batch size takes the two
+ * passes, pass 1 in its running-maximum form. */
+int range_set_temperatures(range_ctx* ctx, float tau_sem, float tau_geo);
 
 /* The same path with the reference's own output contract: the result lands in HOST memory
  * (range/range.py:240 returns a numpy array; range/utils/save.py:27-30 consumes it).  out_host is

@@ -38,7 +38,7 @@ SYMBOLS = (
     "range_host_copy", "range_topk_stream_exact_count", "range_topk_stream_timed",
     "range_set_pv_mode", "range_get_pv_mode", "range_set_keys", "range_debug_raise_async_error",
     "range_scan_stats_at", "range_p1_splits", "range_check_async_error", "range_stream_read_timed",
-    "range_async_error_flag", "range_topk_last",
+    "range_async_error_flag", "range_topk_last", "range_set_temperatures",
 )
 PV_MODES = {"exact": 0, "bf16x3": 1}   # range_set_pv_mode
 
@@ -112,6 +112,7 @@ def load_library() -> C.CDLL:
     lib.range_set_pv_mode.argtypes = [vp, i32]
     lib.range_get_pv_mode.argtypes = [vp]
     lib.range_get_pv_mode.restype = i32
+    lib.range_set_temperatures.argtypes = [vp, f32, f32]
     for name in SYMBOLS:
         getattr(lib, name)
     if lib.range_abi_version() != 9:
@@ -251,6 +252,11 @@ class HipEngine:
         if mode not in PV_MODES:
             raise ValueError(f"pv_mode must be one of {sorted(PV_MODES)}, got {mode!r}")
         _check(self.lib, self.lib.range_set_pv_mode(self._h, PV_MODES[mode]))
+
+    def set_temperatures(self, tau_sem: float = 0.0, tau_geo: float = 0.0) -> None:
+        """The temperatures ``forward`` / ``forward_host`` run at (range_set_temperatures); 0: the model's
+        default.  ``tau_geo`` applies to RANGE+ only."""
+        _check(self.lib, self.lib.range_set_temperatures(self._h, float(tau_sem), float(tau_geo)))
 
     @property
     def pv_mode(self) -> str:

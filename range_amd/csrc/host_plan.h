@@ -377,6 +377,41 @@ inline EncLaunchPlan plan_encoder(int n_cu, int n_slots, int H, int n_layers, bo
     return p;
 }
 
+// The shift of the softmax statistics and the route of a forward, from the temperatures of a call.
+//   SHIFT_CONSTANT     both temperatures <= MAX_TAU_CONSTANT: m = tau * log2(e) (scan_stats_kernel, the
+//                      one-pass kernel of small batches): 2^(-2m) stays a normal float32;
+//   SHIFT_RUNNING_MAX  either above it: pass 1 is sharp_scan_stats_kernel for BOTH heads (m = the
+//                      largest scaled logit), batches of <= 32 queries take the two passes too (the
+//                      one-pass kernel keeps the constant shift and its cap), and the in-scan top-k
+//                      lists do not exist (top-k comes from the kept logits, or from range_topk_stream).
+// Temperatures must be finite, > 0 and <= MAX_TAU_SHARP (tau_geo <= 0: no geographic head); beyond
+// that the softmax is an argmax to float32 precision.  (include/range_hip.h: RANGE_MAX_TAU,
+// RANGE_MAX_TAU_SHARP are the same numbers; range_hip.hip asserts it.)
+constexpr float MAX_TAU_CONSTANT = 43.0f;
+constexpr float MAX_TAU_SHARP = 1000.0f;
+enum ShiftMode { SHIFT_CONSTANT = 0, SHIFT_RUNNING_MAX = 1 };
+struct TempRoute {
+    bool valid = false;          // false: the temperatures are refused (RANGE_ERR_INVALID)
+    ShiftMode shift = SHIFT_CONSTANT;
+    bool one_pass = false;       // a forward of B queries takes attend_small_kernel
+    bool topk_scan_ok = true;    // the in-scan top-k lists exist for this shift
+};
+
+inline bool temperature_ok(float tau, float cap) { return std::isfinite(tau) && tau > 0.f && tau <= cap; }
+
+inline TempRoute plan_temperatures(float tau_sem, float tau_geo, int64_t B, bool small_forward) {
+    TempRoute r;
+    const bool geo = tau_geo > 0.f;
+    if (!temperature_ok(tau_sem, MAX_TAU_SHARP)) return r;
+    if (std::isnan(tau_geo) || (geo && !temperature_ok(tau_geo, MAX_TAU_SHARP))) return r;
+    r.valid = true;
+    const bool sharp = tau_sem > MAX_TAU_CONSTANT || (geo && tau_geo > MAX_TAU_CONSTANT);
+    r.shift = sharp ? SHIFT_RUNNING_MAX : SHIFT_CONSTANT;
+    r.one_pass = !sharp && small_forward && B > 0 && B <= 32;
+    r.topk_scan_ok = !sharp;
+    return r;
+}
+
 // Pass 1 (scan_stats_kernel) over a chunk of B queries, one workgroup per (bank split, query tile),
 // and the streaming top-k over the logits it kept.
 struct Pass1Plan {

@@ -19,6 +19,7 @@
 #include "scan_common.h"
 #include "topk_lists.h"
 #include "pass1.h"
+#include "pass1_sharp.h"
 #include "pass2.h"
 #include "topk_stream.h"
 #include "topk_gemm.h"
@@ -94,6 +95,8 @@ struct range_ctx {
         DevBuf<uint32_t> d_vplanes;      // (ceil(n_rows/32), 4 pieces, 16 tiles, 3 planes, 64 lanes, 8 bf16)
         int64_t vplanes_groups = 0;
     } bank;
+    // range_set_temperatures: the temperatures range_forward / range_forward_host run at (0: the model's default)
+    float tau_sem_set = 0.f, tau_geo_set = 0.f;
     // the queries of the last call and the workspace of the two passes / the one-pass route
     struct Passes {
         DevBuf<double> ws_ehat64;
@@ -300,15 +303,21 @@ int build_vplanes(range_ctx* c) {
     return RANGE_OK;
 }
 
-// Preconditions and scales of every kernel that forms softmax weights with the constant shift
-// m = tau * log2(e): k_sem / k_geo are the temperatures in the kernels' base-2 form (k_geo 0: no
-// geographic head).
-int softmax_scales(range_ctx* c, int64_t B, float tau_sem, float tau_geo, float& k_sem, float& k_geo) {
+static_assert(MAX_TAU_CONSTANT == RANGE_MAX_TAU && MAX_TAU_SHARP == RANGE_MAX_TAU_SHARP, "host_plan.h and range_hip.h disagree");
+
+// Preconditions and scales of every kernel that forms softmax weights: k_sem / k_geo are the
+// temperatures in the kernels' base-2 form (k_geo 0: no geographic head).  max_tau: the cap that fits
+// the caller - RANGE_MAX_TAU for a kernel with the constant shift m = tau * log2(e), RANGE_MAX_TAU_SHARP
+// for one that takes its shift from the statistics (pass 2) or keeps a running maximum.
+int softmax_scales(range_ctx* c, int64_t B, float tau_sem, float tau_geo, float max_tau, float& k_sem, float& k_geo) {
     if (!c->bank.has_bank) return fail(RANGE_ERR_STATE, "bank not set (range_set_bank)");
     if (!c->bank.has_values)
         return fail(RANGE_ERR_STATE, "keys-only bank (range_set_keys): only range_topk_stream runs on it");
     if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (!(tau_sem > 0.f)) return fail(RANGE_ERR_INVALID, "tau_sem must be > 0");
+    if (!plan_temperatures(tau_sem, tau_geo, B, false).valid)
+        return fail(RANGE_ERR_INVALID, "temperatures must be finite, > 0 and at most %g (tau_sem %g, tau_geo %g; tau_geo <= 0: "
+                    "no geographic head): beyond that the softmax is an argmax to float32 precision",
+                    (double)RANGE_MAX_TAU_SHARP, (double)tau_sem, (double)tau_geo);
     // the constant shift m = tau * log2(e) of the softmax statistics needs every logit <= 1:
     // unit keys (range/range.py:85-89).  A bank that skipped that preparation would overflow.
     // (written as !(x <= 1.001): a row holding NaN or infinity makes the largest norm NaN / inf and is
@@ -321,11 +330,9 @@ int softmax_scales(range_ctx* c, int64_t B, float tau_sem, float tau_geo, float&
     if (tau_geo > 0.f && !(c->bank.xyz_norm_max <= 1.001f))
         return fail(RANGE_ERR_INVALID, "bank locations are not unit vectors or not finite (largest row norm %.4f): the geographic "
                     "softmax needs them as range/utils/utils.py:11-16 computes them", (double)c->bank.xyz_norm_max);
-    // the softmax statistics use the constant shift m = tau * log2(e) (scan_stats_kernel): the
-    // smallest term 2^(-2m) must stay a normal float32
-    if (tau_sem > RANGE_MAX_TAU || tau_geo > RANGE_MAX_TAU)
-        return fail(RANGE_ERR_INVALID, "temperatures above %g are not supported (the reference uses 12, 15 and 40)",
-                    (double)RANGE_MAX_TAU);
+    // a kernel with the constant shift m = tau * log2(e): the smallest term 2^(-2m) must stay a normal float32
+    if (tau_sem > max_tau || tau_geo > max_tau)
+        return fail(RANGE_ERR_INVALID, "internal: temperatures above %g reached a constant-shift kernel", (double)max_tau);
     const double LOG2E = 1.4426950408889634;
     k_sem = (float)(tau_sem * LOG2E);
     k_geo = tau_geo > 0.f ? (float)(tau_geo * LOG2E) : 0.f;
@@ -336,7 +343,7 @@ int softmax_scales(range_ctx* c, int64_t B, float tau_sem, float tau_geo, float&
 // n_splits, sk_*) and the outputs are the caller's, from its plan
 int fill_scan_args(range_ctx* c, ScanArgs& a, const float* ehat32, const float* xq, int64_t B,
                    float tau_sem, float tau_geo) {
-    if (int rc = softmax_scales(c, B, tau_sem, tau_geo, a.k_sem, a.k_geo)) return rc;
+    if (int rc = softmax_scales(c, B, tau_sem, tau_geo, RANGE_MAX_TAU_SHARP, a.k_sem, a.k_geo)) return rc;
     a.keys = c->bank.d_keys.p;
     a.xyz4 = c->bank.d_xyz4.p;
     a.values = c->bank.d_values.p;
@@ -625,6 +632,17 @@ int range_set_pv_mode(range_ctx* c, int32_t mode) {
 }
 int32_t range_get_pv_mode(const range_ctx* c) { return c ? c->bank.pv_mode : -1; }
 
+int range_set_temperatures(range_ctx* c, float tau_sem, float tau_geo) {
+    if (!c) return fail(RANGE_ERR_INVALID, "null argument");
+    // 0: the model's default; anything else must be a temperature the kernels take
+    if ((tau_sem != 0.f && !temperature_ok(tau_sem, RANGE_MAX_TAU_SHARP)) || (tau_geo != 0.f && !temperature_ok(tau_geo, RANGE_MAX_TAU_SHARP)))
+        return fail(RANGE_ERR_INVALID, "temperatures must be finite, > 0 and at most %g, or 0 for the model's default (tau_sem %g, tau_geo %g)",
+                    (double)RANGE_MAX_TAU_SHARP, (double)tau_sem, (double)tau_geo);
+    c->tau_sem_set = tau_sem;
+    c->tau_geo_set = tau_geo;
+    return RANGE_OK;
+}
+
 // A persistent kernel that gave up waiting for its other workgroups (possible only when something
 // else holds the GPU's CUs for seconds) has written NaN rows (encoder) / NaN values and -1 indices
 // (top-k) for what it could not finish, and set a word of host memory.  That word is read here - in
@@ -778,6 +796,10 @@ int range_blend(range_ctx* c, const float* G, const float* H, float beta, int64_
                        (hipStream_t)stream, G, H, beta, n4, out);
 }
 
+// pass 1 with a running maximum (pass1_sharp.h); defined at the end of this file: hipcc emits kernels in the
+// order of their first use, and the kernels of the default path keep theirs
+static void (*sharp_scan_kernel(bool geo))(ScanArgs);
+
 // first_query / total_queries / force_splits: range_scan_stats_at (a scan in chunks whose
 // kept logits share one workspace); a plain range_scan_stats is the chunk [0, B) of a scan of B.
 static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32, int64_t B, float tau_sem,
@@ -834,6 +856,12 @@ static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32,
     const bool topk_scan = topk > 0 && !topk_from_kept;
     int rc = fill_scan_args(c, a, ehat32, xq32, B, tau_sem, tau_geo);
     if (rc) return rc;
+    // temperatures above RANGE_MAX_TAU: the running-max form of pass 1 (pass1_sharp.h), for both heads
+    const TempRoute route = plan_temperatures(tau_sem, tau_geo, B, c->sw.small_forward);
+    if (topk_scan && !route.topk_scan_ok)
+        return fail(RANGE_ERR_INVALID, "range_scan_stats(topk > 0) at a temperature above %g needs to keep its logits (this "
+                    "context cannot: RANGE_KEEP_LOGITS=0 or not enough free memory): take the top-k from range_topk_stream",
+                    (double)RANGE_MAX_TAU);
     const Pass1Plan p = plan_pass1(c->n_cu, c->bank.n_rows, B, topk_scan, force_splits, PLAN_CONSTS);
     a.n_blocks = p.n_blocks;
     a.n_qtiles = p.n_qtiles;
@@ -859,7 +887,8 @@ static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32,
                                                         {scan_stats_kernel<false, true>, scan_stats_kernel<false, false>}};
     {
         ProfScope ps(c, RANGE_PROF_SCAN_STATS, s);
-        if (int lrc = launch(scan_kernels[!geo][!topk_scan], dim3((unsigned)p.grid), dim3(256), SCAN_LDS_BYTES, s, a)) return lrc;
+        void (*const kernel)(ScanArgs) = route.shift == SHIFT_RUNNING_MAX ? sharp_scan_kernel(geo) : scan_kernels[!geo][!topk_scan];
+        if (int lrc = launch(kernel, dim3((unsigned)p.grid), dim3(256), SCAN_LDS_BYTES, s, a)) return lrc;
     }
     if (a.logits && keep_logits) {
         c->kept.kept_B = first_query + B;
@@ -1183,6 +1212,8 @@ static int attend_impl(range_ctx* c, const float* ehat32, const float* xq32, int
     hipStream_t s = (hipStream_t)stream;
     const bool geo = tau_geo > 0.f;
     const bool bf16x3 = kept_first >= 0 && c->bank.pv_mode == RANGE_PV_BF16X3;
+    if (bf16x3 && plan_temperatures(tau_sem, tau_geo, B, false).shift == SHIFT_RUNNING_MAX)
+        return fail(RANGE_ERR_INVALID, "pv mode bf16x3 is not supported at temperatures above %g", (double)RANGE_MAX_TAU);
     // (stream-K: the exact kernels only)
     const Pass2Plan p = plan_pass2(c->n_cu, c->bank.n_rows, B, c->sw.p2_streamk && !bf16x3 && !diag_dev, PLAN_CONSTS);
     a.n_blocks = p.n_blocks;
@@ -1283,11 +1314,14 @@ int range_finalize(range_ctx* c, const float* partials, int32_t n_parts, const d
 // heads (tau_geo 0: no geographic head) and the blend the kernels apply
 struct ModelParams { float tau_sem, tau_geo, beta; };
 
-static int model_params(int32_t model, float beta, ModelParams& m) {
+static int model_params(const range_ctx* c, int32_t model, float beta, ModelParams& m) {
     if (model != RANGE_MODEL_RANGE && model != RANGE_MODEL_RANGE_PLUS)
         return fail(RANGE_ERR_INVALID, "unknown model %d", model);
     m.tau_sem = model == RANGE_MODEL_RANGE ? 15.0f : 12.0f;   // range.py:103, 108
     m.tau_geo = model == RANGE_MODEL_RANGE ? 0.0f : 40.0f;    // range.py:109
+    // range_set_temperatures (the reference reads args.temp / args.geo_temp at call time, range.py:215, 234)
+    if (c->tau_sem_set > 0.f) m.tau_sem = c->tau_sem_set;
+    if (c->tau_geo_set > 0.f && model == RANGE_MODEL_RANGE_PLUS) m.tau_geo = c->tau_geo_set;
     m.beta = model == RANGE_MODEL_RANGE ? 1.0f : beta;
     return RANGE_OK;
 }
@@ -1298,7 +1332,7 @@ static int model_params(int32_t model, float beta, ModelParams& m) {
 // e-hat / xq of the B queries are in the context's workspace (range_encode ran on `stream`).
 static int forward_small(range_ctx* c, int64_t B, const ModelParams& m, double* out, hipStream_t s) {
     SmallArgs a{};
-    int rc = softmax_scales(c, B, m.tau_sem, m.tau_geo, a.k_sem, a.k_geo);
+    int rc = softmax_scales(c, B, m.tau_sem, m.tau_geo, RANGE_MAX_TAU, a.k_sem, a.k_geo);
     if (rc) return rc;
     const SmallPlan p = plan_forward_small(c->n_cu, c->bank.n_rows, B, PLAN_CONSTS);
     HIP_TRY(c->pass.ws_small_o.ensure(p.o_floats));
@@ -1347,9 +1381,9 @@ int range_forward(range_ctx* c, const double* lonlat, int64_t B, int32_t model, 
                   double* out, range_stream_t stream) {
     if (!c || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
     ModelParams m;
-    if (int rc = model_params(model, beta, m)) return rc;
+    if (int rc = model_params(c, model, beta, m)) return rc;
     c->pass.ws_queries = 0;
-    if (B > 0 && B <= 32 && c->sw.small_forward) {
+    if (plan_temperatures(m.tau_sem, m.tau_geo, B, c->sw.small_forward).one_pass) {
         // a handful of queries: one pass over the bank (attend_small.h)
         if (int lrc = encode_to_workspace(c, lonlat, B, nullptr, stream)) return lrc;
         c->pass.ws_queries = B;
@@ -1382,7 +1416,7 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
                        double* out_host, range_stream_t stream) {
     if (!c || !lonlat || !out_host) return fail(RANGE_ERR_INVALID, "null argument");
     ModelParams m;
-    if (int rc0 = model_params(model, beta, m)) return rc0;
+    if (int rc0 = model_params(c, model, beta, m)) return rc0;
     if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
     DeviceGuard g(c->device);
     if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
@@ -1403,7 +1437,7 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
     int rc = encode_to_workspace(c, lonlat, B, nullptr, stream);
     if (rc) return rc;
     c->pass.ws_queries = B;
-    if (B <= 32 && c->sw.small_forward) {
+    if (plan_temperatures(m.tau_sem, m.tau_geo, B, c->sw.small_forward).one_pass) {
         // a handful of queries: one pass over the bank, one small copy
         rc = forward_small(c, B, m, c->host.ws_out64.p, s);
         if (rc) return rc;
@@ -1529,3 +1563,9 @@ int range_last_attend_geometry(const range_ctx* c, int32_t* n_query_tiles, int32
 }
 
 }  // extern "C"
+
+static void (*sharp_scan_kernel(bool geo))(ScanArgs) {
+    // [0: with the geographic head, 1: without]
+    static void (*const sharp_kernels[2])(ScanArgs) = {sharp_scan_stats_kernel<true>, sharp_scan_stats_kernel<false>};
+    return sharp_kernels[!geo];
+}

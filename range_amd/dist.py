@@ -9,8 +9,10 @@ decomposes exactly over row shards:
     2. all-gather of the query operands e32 (B,256) and xq (B,4): W*B*1040 B per rank
     3. pass 1 on the local shard for ALL W*B queries -> softmax statistics (m, l) with the
        constant shift m = tau*log2(e) (unit-vector logits), so the l of disjoint shards ADD
-    4. all-gather of the statistics (W*B,4) + merge in rank order (same m, the l add: a fixed
-       order, where an all-reduce's would depend on an element's place in the buffer)
+       (temperatures above 43: m is the shard's largest scaled logit)
+    4. all-gather of the statistics (W*B,4) + merge in rank order (an exact log-sum-exp merge; with
+       the same m the l add: a fixed order, where an all-reduce's would depend on an element's
+       place in the buffer)
     5. pass 2 on the local shard with the GLOBAL statistics -> partial (W*B,1024) f32; partials
        of different shards simply add because the weights are already globally normalised
     6. all-to-all: rank r receives the W partial slices of ITS queries (one direct transfer per
@@ -118,8 +120,12 @@ class ShardedRange:
     min_chunk = 512
 
     def __init__(self, engine, model_name: str = "RANGE+", beta: Optional[float] = 0.5,
-                 group=None, n_chunks: Optional[int] = None):
-        self.tau_sem, self.tau_geo, _, _ = range_model(model_name)
+                 group=None, n_chunks: Optional[int] = None, *, tau_sem: Optional[float] = None,
+                 tau_geo: Optional[float] = None):
+        # (tau_sem / tau_geo: other temperatures than the reference's defaults - the same on every rank;
+        # above 43 every shard's pass 1 keeps a running maximum and the shards' m differ: merge_stats is
+        # an exact log-sum-exp merge either way)
+        self.tau_sem, self.tau_geo, _, _ = range_model(model_name, tau_sem, tau_geo)
         self.beta = float(beta) if self.tau_geo else 1.0        # (RANGE: the semantic retrieval alone)
         self.engine: ShardEngine = engine
         self.group = group

@@ -7,7 +7,7 @@ from argparse import Namespace
 from .range import LocationEncoder, ShardedLocationEncoder
 
 
-def load_model(model_name="RANGE+", pretrained_path=None, device="cuda", **kwargs):
+def load_model(model_name="RANGE+", pretrained_path=None, device="cuda", temp=None, geo_temp=None, **kwargs):
     """Load a RANGE / RANGE+ (or plain SatCLIP) location encoder running on MI355X.
 
     Args:
@@ -16,6 +16,12 @@ def load_model(model_name="RANGE+", pretrained_path=None, device="cuda", **kwarg
         pretrained_path: SatCLIP checkpoint (e.g. satclip-vit16-l40.ckpt); the reference demands
             it for every model name, also those that never read it.
         device: 'cuda' / 'cuda:N'.
+        temp, geo_temp: the softmax temperatures of the semantic / the geographic (RANGE+ only) retrieval
+            instead of the reference's 15 (RANGE), 12 and 40 (RANGE+) - finite, > 0, at most 1000.  They
+            land in ``model.args.temp`` / ``model.args.geo_temp``, which - as in the reference
+            (range.py:215, 234) - are read at every call: ``model.args.temp = 25.0`` changes the next
+            forward.  Up to 43 the kernels are the default ones; above, pass 1 keeps a running maximum
+            and every batch size takes the two passes (not with ``pv_mode='bf16x3'``).
         **kwargs: ``db_path`` (required) - the range_db_*.npz bank; ``beta`` (RANGE+, default 0.5).
             Optional, not in the reference: ``sh_eval`` - 'reference' (default: 'analytic'
             checkpoints evaluate the reference's own generated polynomials, so embeddings agree
@@ -44,6 +50,15 @@ def load_model(model_name="RANGE+", pretrained_path=None, device="cuda", **kwarg
         beta = None
     args = Namespace(location_model_name=model_name, pretrained_path=pretrained_path,
                      device=device, range_db=db_path, beta=beta)           # :45-46
+    if temp is not None or geo_temp is not None:
+        if model_name not in ("RANGE", "RANGE+"):
+            raise ValueError("temp= / geo_temp= apply to the RANGE / RANGE+ models")
+        from .range import check_temperatures
+        check_temperatures(model_name, temp, geo_temp, kwargs.get("pv_mode"))    # (before anything is loaded)
+        if temp is not None:
+            args.temp = float(temp)
+        if geo_temp is not None:
+            args.geo_temp = float(geo_temp)
     for opt in ("sh_eval", "sh_source", "pv_mode", "shards", "row_shards"):
         if opt in kwargs:
             setattr(args, opt, kwargs[opt])

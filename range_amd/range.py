@@ -45,15 +45,41 @@ def _device_of(spec) -> torch.device:
     return dev
 
 
-def range_model(name: str):
+MAX_TEMP_CONSTANT = 43.0  # include/range_hip.h: RANGE_MAX_TAU (the constant-shift kernels)
+MAX_TEMP = 1000.0         # RANGE_MAX_TAU_SHARP
+
+
+def check_temperatures(name: str, temp, geo_temp=None, pv_mode: Optional[str] = None):
+    """Validate the softmax temperatures of "RANGE" / "RANGE+" (``args.temp`` / ``args.geo_temp``; None:
+    the reference's default) -> (tau_sem, tau_geo) floats, tau_geo = 0 for "RANGE".  Pure: no GPU.
+    ValueError for a temperature that is not finite, not > 0 or above 1000 (there the softmax is an
+    argmax to float32 precision), for ``geo_temp`` with plain "RANGE" (it has no geographic head),
+    and for a temperature above 43 together with ``pv_mode='bf16x3'`` (the bf16-plane pass 2 is
+    tuned and tested for the constant-shift range only)."""
+    if name not in ("RANGE", "RANGE+"):
+        raise ValueError("Unimplemented RANGE model")                   # range.py:113-114
+    if name == "RANGE" and geo_temp is not None:
+        raise ValueError("geo_temp applies to RANGE+ only: RANGE has no geographic retrieval")
+    tau_sem = float(TEMP_RANGE if name == "RANGE" else TEMP_RANGE_PLUS) if temp is None else float(temp)
+    tau_geo = 0.0 if name == "RANGE" else (float(TEMP_GEO) if geo_temp is None else float(geo_temp))
+    for what, tau in (("temp", tau_sem),) + ((("geo_temp", tau_geo),) if name == "RANGE+" else ()):
+        if not (np.isfinite(tau) and 0.0 < tau <= MAX_TEMP):
+            raise ValueError(f"{what}={tau!r}: a temperature must be finite, > 0 and at most {MAX_TEMP:g}")
+    if pv_mode == "bf16x3" and max(tau_sem, tau_geo) > MAX_TEMP_CONSTANT:
+        raise ValueError(f"pv_mode='bf16x3' supports temperatures up to {MAX_TEMP_CONSTANT:g} "
+                         f"(temp={tau_sem:g}, geo_temp={tau_geo:g}): use pv_mode='exact'")
+    return tau_sem, tau_geo
+
+
+def range_model(name: str, temp=None, geo_temp=None):
     """"RANGE" / "RANGE+" -> (tau_sem, tau_geo, kernel model id, the reference's banner); tau_geo = 0:
-    no geographic retrieval."""
+    no geographic retrieval.  ``temp`` / ``geo_temp``: other temperatures than the reference's
+    defaults (``check_temperatures``)."""
+    tau_sem, tau_geo = check_temperatures(name, temp, geo_temp)
     if name == "RANGE":                                                 # range.py:102-105
-        return TEMP_RANGE, 0.0, _native.MODEL_RANGE, f"Using RANGE with temperature {TEMP_RANGE}"
-    if name == "RANGE+":                                                # :107-112
-        return (TEMP_RANGE_PLUS, TEMP_GEO, _native.MODEL_RANGE_PLUS,
-                f"Using RANGE+ with temperatures {TEMP_RANGE_PLUS} and {TEMP_GEO}")
-    raise ValueError("Unimplemented RANGE model")                       # :113-114
+        return tau_sem, 0.0, _native.MODEL_RANGE, f"Using RANGE with temperature {tau_sem}"
+    return (tau_sem, tau_geo, _native.MODEL_RANGE_PLUS,                 # :107-112
+            f"Using RANGE+ with temperatures {tau_sem} and {tau_geo}")
 
 
 def attend_any(eng, kept: bool, first: int, e32, xq, tau_sem, tau_geo, beta, stats):
@@ -207,12 +233,35 @@ class _EncoderBase(nn.Module):
     """What the one-GPU and the row-sharded encoder share: ``args``, ``engine``, ``loc_model``."""
 
     def _range_temperatures(self) -> int:
-        """``args.temp`` / ``args.geo_temp`` and the banner of RANGE / RANGE+; returns the kernel model id."""
-        self.args.temp, tau_geo, model_id, banner = range_model(self.location_model_name)
+        """``args.temp`` / ``args.geo_temp`` (the reference's defaults unless ``load_model(temp=,
+        geo_temp=)`` gave others) and the banner of RANGE / RANGE+; returns the kernel model id."""
+        a = self.args
+        check_temperatures(self.location_model_name, getattr(a, "temp", None), getattr(a, "geo_temp", None),
+                           getattr(a, "pv_mode", None))
+        a.temp, tau_geo, model_id, banner = range_model(self.location_model_name, getattr(a, "temp", None),
+                                                        getattr(a, "geo_temp", None))
         if tau_geo:
-            self.args.geo_temp = tau_geo
+            a.geo_temp = tau_geo
         print(banner)
+        # what the engine runs at: its defaults are the reference's (range_set_temperatures)
+        self._engine_temps = range_model(self.location_model_name)[:2]
         return model_id
+
+    def _temperatures(self):
+        """``args.temp`` / ``args.geo_temp`` as they are NOW - the reference reads them at every call
+        (range.py:215, 234), like ``args.beta`` - validated -> (tau_sem, tau_geo); tau_geo = 0: RANGE."""
+        a = self.args
+        plus = self.location_model_name == "RANGE+"
+        return check_temperatures(self.location_model_name, a.temp, a.geo_temp if plus else None,
+                                  getattr(a, "pv_mode", None))
+
+    def _sync_engine_temperatures(self):
+        """The engine's forward at the current temperatures; a call into the library only when they changed."""
+        temps = self._temperatures()
+        if temps != self._engine_temps:
+            self.engine.set_temperatures(*temps)
+            self._engine_temps = temps
+        return temps
 
     def _make_engine(self, enc, bank, row_offset: int = 0):
         a = self.args
@@ -320,6 +369,7 @@ class LocationEncoder(_EncoderBase):
         an empty (0,1280) array as well)"""
         B = x.shape[0]
         beta = 1.0 if self._model_id == _native.MODEL_RANGE else float(self.args.beta)
+        self._sync_engine_temperatures()
         if return_device:
             run, out = self.engine.forward, torch.empty((B, _native.OUT_DIM), dtype=torch.float64, device=x.device)
         else:
@@ -347,15 +397,16 @@ class LocationEncoder(_EncoderBase):
         if self._model_id != _native.MODEL_RANGE_PLUS:
             raise ValueError("sweep() is defined for RANGE+ only")
         betas = [float(b) for b in betas]
+        tau_sem, tau_geo = self._temperatures()
         x = self._coords(coords)
         B = x.shape[0]
         out = torch.empty((len(betas), B, _native.OUT_DIM), dtype=torch.float64, device=x.device)
         eng = self.engine
         for i in range(0, B, self.chunk_size):
             e64, e32, xq = eng.encode(x[i:i + self.chunk_size])
-            st = eng.scan_stats(e32, xq, TEMP_RANGE_PLUS, TEMP_GEO, keep_logits=True)
+            st = eng.scan_stats(e32, xq, tau_sem, tau_geo, keep_logits=True)
             kept = eng.kept_queries() == e32.shape[0]      # both passes 2 from the kept logits
-            H, G = (attend_any(eng, kept, 0, e32, xq, TEMP_RANGE_PLUS, TEMP_GEO, b, st) for b in (1.0, 0.0))
+            H, G = (attend_any(eng, kept, 0, e32, xq, tau_sem, tau_geo, b, st) for b in (1.0, 0.0))
             for j, b in enumerate(betas):
                 out[j, i:i + e64.shape[0]] = eng.finalize(eng.blend(G, H, b), e64)
         return out if return_device else self._to_host(out)
@@ -437,7 +488,8 @@ class ShardedLocationEncoder(_EncoderBase):
             raise ValueError(f"bank of {self.n_bank_rows} rows cannot be sharded over {self.row_shards} ranks")
         self.row_range = shard_rows(bank.n_rows, self.row_shards, shard_index)
         self.engine = self._make_engine(enc, bank.rows(*self.row_range), row_offset=self.row_range[0])
-        self.sharded = ShardedRange(self.engine, self.location_model_name, args.beta, group=self.shard_group)
+        self.sharded = ShardedRange(self.engine, self.location_model_name, args.beta, group=self.shard_group,
+                                    tau_sem=args.temp, tau_geo=getattr(args, "geo_temp", None))
         self.loc_model = SatCLIPLocationModel(self.engine, enc)          # range.py:83-84 (replicated on every rank)
         self._freeze()
 
@@ -476,6 +528,7 @@ class ShardedLocationEncoder(_EncoderBase):
         once, the per-shard candidates merge through ONE all-gather (``ShardedRange.forward``)."""
         x = self._coords(coords)
         k = None if return_topk is None else _topk_arg(return_topk)
+        self.sharded.tau_sem, self.sharded.tau_geo = self._temperatures()
         if local:
             res = self.sharded.embed(x, topk=k)
             if not k:
@@ -496,6 +549,7 @@ class ShardedLocationEncoder(_EncoderBase):
         if self.location_model_name != "RANGE+":
             raise ValueError("sweep() is defined for RANGE+ only")
         x = self._coords(coords)
+        self.sharded.tau_sem, self.sharded.tau_geo = self._temperatures()
         if local:
             out = self.sharded.embed_sweep(x, betas)
             return out if return_device else self._to_host(out)
