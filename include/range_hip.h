@@ -325,6 +325,31 @@ int range_attend_kept(range_ctx* ctx, int64_t first_query, const float* xq32_dev
                       float tau_sem, float tau_geo, float beta, const float* stats_global_dev,
                       float* partial_dev, range_stream_t stream);
 
+/* Softmax statistics of the queries [first_query, first_query + B) of the scan whose logits this
+ * context keeps, at n_taus temperature pairs, WITHOUT recomputing e . K^T: the kept dot products are
+ * un-scaled, so one read of them (4 bytes per (query, row), HBM-bound) gives the statistics of any
+ * temperatures; the geographic logit is three products from the bank's locations and xq32_dev.  For
+ * temperature sweeps: one scan, one call here for all the pairs of the grid, then range_attend_kept
+ * per temperature.  No reference counterpart.
+ *   taus_sem_host / taus_geo_host : n_taus temperatures each, HOST arrays; pair p is (taus_sem[p],
+ *                taus_geo[p]); taus_geo[p] <= 0: no geographic head for that pair ({-1e30, 0}).  A pair
+ *                with either temperature above RANGE_MAX_TAU takes the running-maximum form for both of
+ *                its heads, as range_scan_stats does; the other pairs of the call do not matter.
+ *   n_splits   : bank splits, as range_scan_stats_at's (0: what a scan of B queries chooses; the same
+ *                clamp applies).
+ *   stats_dev  : (n_taus, B, 4) float32.
+ * CONTRACT: stats_dev[p] equals BIT FOR BIT what range_scan_stats / range_scan_stats_at writes for the
+ * same queries, pair and split count - whatever the other pairs of the call are, and whatever
+ * temperatures the scan that kept the logits ran at.  Statistics of shards merge through
+ * range_merge_stats as pass 1's do.  More than 8 pairs run as several launches.
+ * RANGE_ERR_STATE: nothing kept, or the bank changed since the logits were kept.  RANGE_ERR_INVALID:
+ * first_query not a multiple of 64 or the range exceeds the kept queries; n_taus < 1 or n_splits < 0; a
+ * tau_sem that is not finite, not > 0 or above RANGE_MAX_TAU_SHARP, or such a tau_geo when it is > 0; a
+ * bank whose norms exceed 1.001 (as range_scan_stats). */
+int range_stats_kept(range_ctx* ctx, int64_t first_query, const float* xq32_dev, int64_t B,
+                     int32_t n_taus, const float* taus_sem_host, const float* taus_geo_host,
+                     int32_t n_splits, float* stats_dev, range_stream_t stream);
+
 /* The blend of range/range.py:238 on its own, with the reference's float32 rounding:
  * out = (1-beta)*G + beta*H over (B,1024) float32.  For beta sweeps: G = range_attend(beta=0),
  * H = range_attend(beta=1) once, then one blend + finalize per beta. */
@@ -375,7 +400,8 @@ int range_last_attend_geometry(const range_ctx* ctx, int32_t* n_query_tiles, int
  * collecting (and clears earlier samples); range_profile_read synchronises with the recorded
  * events and returns the summed duration and the number of launches of one kernel. */
 enum { RANGE_PROF_ENCODER = 0, RANGE_PROF_SCAN_STATS = 1, RANGE_PROF_ATTEND = 2,
-       RANGE_PROF_TOPK_STREAM = 3, RANGE_PROF_TOPK_MERGE = 4, RANGE_PROF_KINDS = 5 };
+       RANGE_PROF_TOPK_STREAM = 3, RANGE_PROF_TOPK_MERGE = 4, RANGE_PROF_KEPT_STATS = 5,
+       RANGE_PROF_KINDS = 6 };
 int range_profile_enable(range_ctx* ctx, int32_t on);
 int range_profile_read(range_ctx* ctx, int32_t which, double* total_ms, int32_t* launches);
 

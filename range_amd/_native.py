@@ -22,7 +22,7 @@ KEY_DIM, VAL_DIM, OUT_DIM = 256, 1024, 1280
 SH_ANALYTIC, SH_CLOSED_FORM = 0, 1
 MODEL_RANGE, MODEL_RANGE_PLUS = 0, 1
 MAX_TOPK = 16
-PROF_ENCODER, PROF_SCAN_STATS, PROF_ATTEND, PROF_TOPK_STREAM, PROF_TOPK_MERGE = 0, 1, 2, 3, 4
+PROF_ENCODER, PROF_SCAN_STATS, PROF_ATTEND, PROF_TOPK_STREAM, PROF_TOPK_MERGE, PROF_KEPT_STATS = 0, 1, 2, 3, 4, 5
 COORD_DIRECT, COORD_CARTESIAN3D, COORD_WRAP = 0, 1, 2   # range_coord_features(mode)
 COORD_DIMS = {COORD_DIRECT: 2, COORD_CARTESIAN3D: 3, COORD_WRAP: 4}
 
@@ -38,7 +38,7 @@ SYMBOLS = (
     "range_host_copy", "range_topk_stream_exact_count", "range_topk_stream_timed",
     "range_set_pv_mode", "range_get_pv_mode", "range_set_keys", "range_debug_raise_async_error",
     "range_scan_stats_at", "range_p1_splits", "range_check_async_error", "range_stream_read_timed",
-    "range_async_error_flag", "range_topk_last", "range_set_temperatures",
+    "range_async_error_flag", "range_topk_last", "range_set_temperatures", "range_stats_kept",
 )
 PV_MODES = {"exact": 0, "bf16x3": 1}   # range_set_pv_mode
 
@@ -88,6 +88,7 @@ def load_library() -> C.CDLL:
     lib.range_p1_splits.restype = i32
     lib.range_attend_kept.argtypes = [vp, i64, vp, i64, f32, f32, f32, vp, vp, vp]
     lib.range_kept_queries.argtypes = [vp]
+    lib.range_stats_kept.argtypes = [vp, i64, vp, i64, i32, vp, vp, i32, vp, vp]
     lib.range_kept_queries.restype = i64
     lib.range_merge_stats.argtypes = [vp, vp, i32, i64, vp, vp]
     lib.range_merge_topk.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp]
@@ -394,6 +395,22 @@ class HipEngine:
                                                     self._stream()))
         return out
 
+    def stats_kept(self, first_query: int, xq: torch.Tensor, taus, n_splits: int = 0) -> torch.Tensor:
+        """The softmax statistics of queries [first_query, first_query + len(xq)) of the last kept scan
+        at every temperature pair of ``taus`` - a sequence of (tau_sem, tau_geo); tau_geo <= 0: no
+        geographic head - from the kept logits: (len(taus), B, 4), every pair bit for bit what
+        ``scan_stats`` / ``scan_stats_at`` gives at its temperatures and ``n_splits`` (range_hip.h:
+        range_stats_kept)."""
+        self._t(xq, torch.float32, (4,))
+        pairs = [(float(s), float(g)) for s, g in taus]
+        B, P = xq.shape[0], len(pairs)
+        ts = (C.c_float * max(P, 1))(*[p[0] for p in pairs])
+        tg = (C.c_float * max(P, 1))(*[p[1] for p in pairs])
+        stats = self._empty((max(P, 1), B, 4), torch.float32)      # (an empty list is the library's to refuse)
+        _check(self.lib, self.lib.range_stats_kept(self._h, first_query, xq.data_ptr(), B, P, ts, tg, n_splits,
+                                                   stats.data_ptr(), self._stream()))
+        return stats[:P]
+
     def topk_stream(self, e32: torch.Tensor, k: int):
         """Small-batch top-k by the HBM-streaming kernel (see range_hip.h)."""
         self._t(e32, torch.float32, (KEY_DIM,))
@@ -532,7 +549,7 @@ class HipEngine:
         _check(self.lib, self.lib.range_profile_enable(self._h, 1 if on else 0))
 
     def profile_read(self, which: int) -> Tuple[float, int]:
-        """(summed device ms, launches) of kernel ``which`` (0 encoder, 1 scan_stats, 2 attend)
+        """(summed device ms, launches) of kernel ``which`` (0 encoder, 1 scan_stats, 2 attend, ... 5 stats_kept)
         since profile_enable(); measured with HIP events on the launch stream."""
         ms, n = C.c_double(), C.c_int32()
         _check(self.lib, self.lib.range_profile_read(self._h, which, C.byref(ms), C.byref(n)))

@@ -448,6 +448,41 @@ inline Pass1Plan plan_pass1(int n_cu, int64_t n_rows, int64_t B, bool topk_scan,
     return p;
 }
 
+// Statistics from the kept logits (pass1_kept.h: kept_stats_kernel) for B queries at n_pairs temperature
+// pairs: pass 1's decomposition - one workgroup per (bank split, query tile) - with up to max_pairs pairs
+// per launch; every pair's parts are then merged as pass 1's are.
+struct KeptStatsPlan {
+    int n_qtiles = 0, n_blocks = 0, n_splits = 0;
+    int grid = 0;               // n_splits * n_qtiles
+    bool merge_by_wave = false;
+    struct Group { int first, count; };
+    std::vector<Group> groups;  // the launches: pairs [first, first + count), count <= max_pairs
+    size_t part_floats = 0;     // parts of ONE pair: n_splits * B * 4
+    size_t ws_floats = 0;       // workspace: the parts of the largest group
+};
+
+// the shift of one pair's statistics: the rule of pass 1 (either temperature above 43: the running maximum
+// for both heads)
+inline ShiftMode kept_pair_shift(float tau_sem, float tau_geo) { return plan_temperatures(tau_sem, tau_geo, 0, false).shift; }
+
+// force_splits: the caller's split count (0: what a scan of B queries chooses) - the rule of
+// range_scan_stats_at, clamp included, so that the parts are those of the scan
+inline KeptStatsPlan plan_kept_stats(int n_cu, int64_t n_rows, int64_t B, int n_pairs, int force_splits, int max_pairs,
+                                     const PlanConsts& K) {
+    KeptStatsPlan p;
+    const Pass1Plan s = plan_pass1(n_cu, n_rows, B, false, force_splits, K);
+    p.n_qtiles = s.n_qtiles;
+    p.n_blocks = s.n_blocks;
+    p.n_splits = s.n_splits;
+    p.grid = s.grid;
+    p.merge_by_wave = s.merge_by_wave;
+    p.part_floats = s.part_floats;
+    for (int first = 0; first < n_pairs; first += max_pairs)
+        p.groups.push_back({first, std::min(max_pairs, n_pairs - first)});
+    p.ws_floats = p.part_floats * (size_t)std::min(max_pairs, std::max(n_pairs, 0));
+    return p;
+}
+
 // Pass 2 (attend_kernel / attend_stored_kernel / attend_bf16x3_kernel) over B queries.
 struct Pass2Plan {
     int n_qtiles = 0, n_blocks = 0;

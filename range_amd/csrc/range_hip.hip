@@ -20,6 +20,7 @@
 #include "topk_lists.h"
 #include "pass1.h"
 #include "pass1_sharp.h"
+#include "pass1_kept.h"
 #include "pass2.h"
 #include "topk_stream.h"
 #include "topk_gemm.h"
@@ -110,6 +111,7 @@ struct range_ctx {
     // bank blocks, 1 KB tiles (scan_common.h: logit_tile); kept_B == 0: nothing kept
     struct Kept {
         DevBuf<float> ws_logits, ws_rowmax, ws_theta;
+        DevBuf<float> ws_stat_parts;     // range_stats_kept: the per-split parts of one launch's pairs
         int64_t kept_B = 0, kept_total = 0;
         int32_t kept_blocks = 0;
         bool warned_no_keep = false;
@@ -799,6 +801,8 @@ int range_blend(range_ctx* c, const float* G, const float* H, float beta, int64_
 // pass 1 with a running maximum (pass1_sharp.h); defined at the end of this file: hipcc emits kernels in the
 // order of their first use, and the kernels of the default path keep theirs
 static void (*sharp_scan_kernel(bool geo))(ScanArgs);
+// the statistics from the kept logits (pass1_kept.h), likewise
+static void (*kept_stats_kernel_for(int n_pairs, bool geo))(KeptStatsArgs);
 
 // first_query / total_queries / force_splits: range_scan_stats_at (a scan in chunks whose
 // kept logits share one workspace); a plain range_scan_stats is the chunk [0, B) of a scan of B.
@@ -1279,6 +1283,63 @@ int range_attend(range_ctx* c, const float* ehat32, const float* xq32, int64_t B
 
 int64_t range_kept_queries(const range_ctx* c) { return c ? c->kept.kept_B : 0; }
 
+int range_stats_kept(range_ctx* c, int64_t first_query, const float* xq32, int64_t B, int32_t n_taus,
+                     const float* taus_sem, const float* taus_geo, int32_t n_splits, float* stats,
+                     range_stream_t stream) {
+    if (!c || !xq32 || !taus_sem || !taus_geo || !stats) return fail(RANGE_ERR_INVALID, "null argument");
+    if (n_taus < 1) return fail(RANGE_ERR_INVALID, "n_taus must be >= 1");
+    if (n_splits < 0) return fail(RANGE_ERR_INVALID, "n_splits must be >= 0");
+    if (c->kept.kept_B <= 0) return fail(RANGE_ERR_STATE, "no kept logits (range_scan_stats with keep_logits)");
+    if (first_query < 0 || first_query % QTILE != 0)
+        return fail(RANGE_ERR_INVALID, "first kept query must be a non-negative multiple of %d", QTILE);
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (first_query + B > c->kept.kept_B)
+        return fail(RANGE_ERR_INVALID, "queries [%lld, %lld) exceed the %lld kept", (long long)first_query,
+                    (long long)(first_query + B), (long long)c->kept.kept_B);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const KeptStatsPlan p = plan_kept_stats(c->n_cu, c->bank.n_rows, B, n_taus, n_splits, KEPT_MAX_PAIRS, PLAN_CONSTS);
+    KeptStatsArgs a{};
+    // every pair: the checks and scales of range_scan_stats (bank, temperatures, norms)
+    std::vector<float> k_sem((size_t)n_taus), k_geo((size_t)n_taus);
+    for (int i = 0; i < n_taus; ++i)
+        if (int rc = softmax_scales(c, B, taus_sem[i], taus_geo[i], RANGE_MAX_TAU_SHARP, k_sem[i], k_geo[i])) return rc;
+    if (p.n_blocks != c->kept.kept_blocks) return fail(RANGE_ERR_STATE, "bank changed since the logits were kept");
+    HIP_TRY(c->kept.ws_stat_parts.ensure(p.ws_floats));
+    a.logits = c->kept.ws_logits.p;
+    a.xyz4 = c->bank.d_xyz4.p;
+    a.xq = xq32;
+    a.out = c->kept.ws_stat_parts.p;
+    a.B = B;
+    a.n_valid = c->bank.n_rows;
+    a.n_blocks = p.n_blocks;
+    a.n_qtiles = p.n_qtiles;
+    a.n_splits = p.n_splits;
+    a.qt_offset = (int32_t)(first_query / QTILE);
+    const int per_wg = p.merge_by_wave ? 4 : 256;      // queries of a merging workgroup: one per wave, or per thread
+    for (const KeptStatsPlan::Group& grp : p.groups) {
+        a.sharp_mask = a.geo_mask = 0u;
+        for (int i = 0; i < grp.count; ++i) {
+            const float ts = taus_sem[grp.first + i], tg = taus_geo[grp.first + i];
+            a.k_sem[i] = k_sem[grp.first + i];
+            a.k_geo[i] = k_geo[grp.first + i];
+            if (kept_pair_shift(ts, tg) == SHIFT_RUNNING_MAX) a.sharp_mask |= 1u << i;
+            if (tg > 0.f) a.geo_mask |= 1u << i;
+        }
+        {
+            ProfScope ps(c, RANGE_PROF_KEPT_STATS, s);
+            if (int rc = launch(kept_stats_kernel_for(grp.count, a.geo_mask != 0u), dim3((unsigned)p.grid), dim3(256), 0, s, a)) return rc;
+        }
+        for (int i = 0; i < grp.count; ++i)
+            if (int rc = launch(p.merge_by_wave ? merge_stats_wave_kernel : merge_stats_kernel, dim3((unsigned)((B + per_wg - 1) / per_wg)),
+                                dim3(256), 0, s, c->kept.ws_stat_parts.p + (size_t)i * p.part_floats, p.n_splits, B,
+                                stats + (size_t)(grp.first + i) * B * 4))
+                return rc;
+    }
+    return RANGE_OK;
+}
+
 int range_attend_kept(range_ctx* c, int64_t first_query, const float* xq32, int64_t B, float tau_sem,
                       float tau_geo, float beta, const float* stats_global, float* partial,
                       range_stream_t stream) {
@@ -1568,4 +1629,14 @@ static void (*sharp_scan_kernel(bool geo))(ScanArgs) {
     // [0: with the geographic head, 1: without]
     static void (*const sharp_kernels[2])(ScanArgs) = {sharp_scan_stats_kernel<true>, sharp_scan_stats_kernel<false>};
     return sharp_kernels[!geo];
+}
+
+static void (*kept_stats_kernel_for(int n_pairs, bool geo))(KeptStatsArgs) {
+    // [pairs of the launch - 1][0: some pair has a geographic head, 1: none]
+    static void (*const kept_kernels[KEPT_MAX_PAIRS][2])(KeptStatsArgs) = {
+        {kept_stats_kernel<1, true>, kept_stats_kernel<1, false>}, {kept_stats_kernel<2, true>, kept_stats_kernel<2, false>},
+        {kept_stats_kernel<3, true>, kept_stats_kernel<3, false>}, {kept_stats_kernel<4, true>, kept_stats_kernel<4, false>},
+        {kept_stats_kernel<5, true>, kept_stats_kernel<5, false>}, {kept_stats_kernel<6, true>, kept_stats_kernel<6, false>},
+        {kept_stats_kernel<7, true>, kept_stats_kernel<7, false>}, {kept_stats_kernel<8, true>, kept_stats_kernel<8, false>}};
+    return kept_kernels[n_pairs - 1][!geo];
 }

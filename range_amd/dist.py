@@ -41,7 +41,7 @@ from typing import Optional, Protocol, Tuple
 import torch
 import torch.distributed as dist
 
-from .range import attend_any, range_model
+from .range import attend_any, range_model, sweep_plan
 
 
 def shard_rows(n_rows: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -64,6 +64,12 @@ class ShardEngine(Protocol):
     def finalize(self, partials, e64, out=None): ...   # (W,B,1024), (B,256) f64 -> (B,1280) f64 (into ``out``)
     def topk_stream(self, e32, k: int): ...            # -> values (B,k) f32, global rows (B,k) i64
     def merge_topk(self, vals, idxs): ...              # (W,B,k) each -> (B,k) each
+
+
+class SweepShardEngine(ShardEngine, Protocol):
+    """What a temperature sweep (``ShardedRange.sweep(..., temps=, geo_temps=)``) calls in addition."""
+
+    def stats_kept(self, first_query, xq, taus, n_splits=0): ...   # (P,B,4): the statistics at P (tau_sem, tau_geo) pairs, from the kept logits
 
 
 def start_collective(kind: str, src: torch.Tensor, group=None, dst: Optional[torch.Tensor] = None,
@@ -446,17 +452,20 @@ class ShardedRange:
 
     @torch.no_grad()
     def embed_sweep(self, lonlat: torch.Tensor, betas, chunk: Optional[int] = None,
-                    out: Optional[torch.Tensor] = None, b_max: Optional[int] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, b_max: Optional[int] = None, *, temps=None,
+                    geo_temps=None) -> torch.Tensor:
         """``embed`` for several beta values at once (one pass 1 and two passes 2 per step whatever
-        the number of betas): (len(betas), B, 1280) float64 on the device."""
-        betas = [float(b) for b in betas]
+        the number of betas): (len(betas), B, 1280) float64 on the device.  ``temps`` / ``geo_temps``:
+        the temperature sweep of ``sweep`` - (T, G, nb, B, 1280), RANGE: (T, B, 1280)."""
+        plan = self._sweep_plan(betas, temps, geo_temps)
+        lead = (len([float(b) for b in betas]),) if plan is None else plan.lead
         B = lonlat.shape[0]
         if out is None:
-            out = torch.empty((len(betas), B, 1280), dtype=torch.float64, device=lonlat.device)
+            out = torch.empty(lead + (B, 1280), dtype=torch.float64, device=lonlat.device)
         for lo, n_own, q in self._steps(lonlat, chunk, b_max):
-            res = self.sweep(q, betas)
+            res = self.sweep(q, betas, temps=temps, geo_temps=geo_temps)
             if n_own:
-                out[:, lo:lo + n_own] = res[:, :n_own]
+                out[..., lo:lo + n_own, :] = res[..., :n_own, :]
         return out
 
     @torch.no_grad()
@@ -472,13 +481,27 @@ class ShardedRange:
                 ti[lo:lo + n_own] = i[:n_own]
         return tv, ti
 
+    def _sweep_plan(self, betas, temps, geo_temps):
+        name = "RANGE+" if self.tau_geo > 0.0 else "RANGE"
+        return sweep_plan(name, betas, temps, geo_temps, self.tau_sem, self.tau_geo or None, self.beta)
+
     @torch.no_grad()
-    def sweep(self, lonlat: torch.Tensor, betas) -> torch.Tensor:
+    def sweep(self, lonlat: torch.Tensor, betas=None, temps=None, geo_temps=None) -> torch.Tensor:
         """RANGE+ embeddings of this rank's queries for several beta values (BASELINE config
         "beta sweep ... 8xMI355X"): one pass 1, per chunk TWO passes 2 on its kept logits (beta = 1:
         the semantic retrieval H, beta = 0: the geographic G), two exchanges, then one blend
         (range.py:238, applied per shard partial - the blend is linear) + finalize per beta.
-        Returns (len(betas), B, 1280) float64 on the device."""
+        Returns (len(betas), B, 1280) float64 on the device.
+
+        ``temps`` / ``geo_temps`` (``range.sweep_plan``: the pairing rule and the result shapes of
+        ``LocationEncoder.sweep``): a temperature sweep from the same ONE pass 1.  Per chunk the shard's
+        statistics of every pair come from its kept logits (``stats_kept``, with the bank splits of the
+        scan) and travel in ONE all-gather - (P n, 4) rows: the merge is row-wise -, then one pass 2 and
+        one exchange per semantic and per geographic temperature, a blend + finalize per grid point.
+        (T, G, nb, B, 1280); RANGE: (T, B, 1280).  Logits not kept: ``scan_stats_at`` per pair."""
+        plan = self._sweep_plan(betas, temps, geo_temps)
+        if plan is not None:
+            return self._temperature_sweep(lonlat, plan)
         if self.tau_geo <= 0.0:
             raise ValueError("sweep() is defined for RANGE+ only")
         betas = [float(b) for b in betas]
@@ -500,6 +523,42 @@ class ShardedRange:
             for j, b in enumerate(betas):
                 mix = self.engine.blend(rG, rH, b)                   # (W*n, 1024): per-shard partials
                 out[j, lo:hi] = self.engine.finalize(mix.reshape(W, hi - lo, mix.shape[1]), e)
+        return out
+
+    def _temperature_sweep(self, lonlat: torch.Tensor, plan) -> torch.Tensor:
+        W, B = self.world, lonlat.shape[0]
+        eng = self.engine
+        e64, e32_all, xq_all, chunks, stats_of, kept = self._scan(lonlat)
+        total = W * B
+        n_splits = eng.p1_splits(W * max(hi - lo for lo, hi in chunks))      # (what _scan gave every chunk)
+        P, T = len(plan.pairs), len(plan.temps)
+        pending = []
+        for ci, (lo, hi) in enumerate(chunks):
+            first, n = W * lo, W * (hi - lo)
+            sl = slice(first, first + n)
+            stats_of[ci]()                                   # (the scan's own statistics: not used, their collective is drained)
+            if kept:
+                local = eng.stats_kept(first, xq_all[sl], plan.pairs, n_splits=n_splits)
+            else:
+                local = torch.stack([eng.scan_stats_at(e32_all[sl], xq_all[sl], ts, tg, first, total, n_splits=n_splits)
+                                     for ts, tg in plan.pairs])
+            # ONE all-gather for the statistics of all pairs: rows (pair, query)
+            st = self._stats_start(local.reshape(P * n, 4), f"sweep_stats{ci}")().view(P, n, 4)
+            parts = [attend_any(eng, kept, first, e32_all[sl], xq_all[sl], ts, tg, 1.0 if p < T else 0.0, st[p].contiguous())
+                     for p, (ts, tg) in enumerate(plan.pairs)]
+            pending.append(([self._exchange(part, f"tsweep{ci}:{j}") for j, part in enumerate(parts)], lo, hi))
+        out = torch.empty(plan.lead + (B, e64.shape[1] + 1024), dtype=torch.float64, device=e64.device)
+        for gots, lo, hi in pending:
+            heads = [g() for g in gots]
+            e = e64[lo:hi].contiguous()
+            for ti in range(T):
+                if not plan.geo_temps:                       # RANGE: the semantic retrieval alone
+                    out[ti, lo:hi] = eng.finalize(heads[ti].reshape(W, hi - lo, -1), e)
+                    continue
+                for gi in range(len(plan.geo_temps)):
+                    for bi, b in enumerate(plan.betas):
+                        mix = eng.blend(heads[T + gi], heads[ti], b)             # (W*n, 1024): per-shard partials
+                        out[ti, gi, bi, lo:hi] = eng.finalize(mix.reshape(W, hi - lo, mix.shape[1]), e)
         return out
 
     @torch.no_grad()

@@ -90,6 +90,55 @@ def attend_any(eng, kept: bool, first: int, e32, xq, tau_sem, tau_geo, beta, sta
     return eng.attend(e32, xq, tau_sem, tau_geo, beta, stats)
 
 
+class SweepPlan:
+    """What a temperature sweep runs (``sweep_plan``): the validated lists, the temperature pairs whose
+    statistics it needs and the leading dimensions of its result."""
+
+    def __init__(self, temps, geo_temps, betas, pairs, lead):
+        self.temps, self.geo_temps, self.betas, self.pairs, self.lead = temps, geo_temps, betas, pairs, lead
+
+    @property
+    def scan_taus(self):
+        """The temperatures of the one scan that keeps the logits: the first of each list."""
+        return self.temps[0], (self.geo_temps[0] if self.geo_temps else 0.0)
+
+
+def sweep_plan(name: str, betas, temps, geo_temps, args_temp, args_geo_temp=None, args_beta=None,
+               pv_mode: Optional[str] = None) -> Optional[SweepPlan]:
+    """The arguments of ``sweep(coords, betas, temps=, geo_temps=)`` -> a ``SweepPlan``, or None for the
+    plain beta sweep (both lists None).  Pure: no GPU.
+
+    RANGE+ with either list: a missing list is ``[args_temp]`` / ``[args_geo_temp]``, ``betas=None`` is
+    ``[args_beta]``; the result is (T, G, nb, B, 1280).  RANGE with ``temps``: ``betas`` and
+    ``geo_temps`` must be None; the result is (T, B, 1280).  Every value goes through
+    ``check_temperatures`` (its bf16x3 rule included); an empty list is a ValueError.
+
+    Pairs: the semantic retrieval H_i runs at (temps[i], 0) - no geographic head, what plain RANGE runs
+    at that temperature - and the geographic retrieval G_j at (TEMP_RANGE_PLUS, geo_temps[j]), its
+    semantic weight multiplied by beta = 0: a head's bits do not depend on what else is in the lists."""
+    if temps is None and geo_temps is None:
+        return None
+    if name not in ("RANGE", "RANGE+"):
+        raise ValueError("sweep() is defined for RANGE / RANGE+ only")
+    if name == "RANGE":
+        if geo_temps is not None:
+            raise ValueError("geo_temps applies to RANGE+ only: RANGE has no geographic retrieval")
+        if betas is not None:
+            raise ValueError("betas applies to RANGE+ only: RANGE has no blend")
+    ts = [args_temp] if temps is None else list(temps)
+    gs = [] if name == "RANGE" else ([args_geo_temp] if geo_temps is None else list(geo_temps))
+    bs = [] if name == "RANGE" else ([args_beta] if betas is None else list(betas))
+    for what, lst in (("temps", ts),) + ((("geo_temps", gs), ("betas", bs)) if name == "RANGE+" else ()):
+        if len(lst) == 0:
+            raise ValueError(f"{what} must not be empty")
+    ts = [check_temperatures(name, t, None, pv_mode)[0] for t in ts]
+    gs = [check_temperatures(name, None, g, pv_mode)[1] for g in gs]
+    bs = [float(b) for b in bs]
+    pairs = [(t, 0.0) for t in ts] + [(float(TEMP_RANGE_PLUS), g) for g in gs]
+    lead = (len(ts),) if name == "RANGE" else (len(ts), len(gs), len(bs))
+    return SweepPlan(ts, gs, bs, pairs, lead)
+
+
 def _as_coords(coords, device) -> torch.Tensor:
     if not torch.is_tensor(coords):
         coords = torch.as_tensor(np.asarray(coords))
@@ -388,14 +437,38 @@ class LocationEncoder(_EncoderBase):
         return (out, tv, ti) if k else out
 
     @torch.no_grad()
-    def sweep(self, coords, betas, return_device: bool = False):
+    def sweep(self, coords, betas=None, return_device: bool = False, *, temps=None, geo_temps=None):
         """RANGE+ embeddings of the same queries for several beta values (BASELINE config
         "beta sweep").  beta only enters the blend of range.py:238, so the semantic retrieval H
         and the geographic retrieval G are computed ONCE (two pass-2 launches instead of one per
         beta) and blended per beta with the reference's float32 rounding.
-        Returns an array (len(betas), B, 1280) float64 (host ndarray, or device tensor)."""
+        Returns an array (len(betas), B, 1280) float64 (host ndarray, or device tensor).
+
+        ``temps`` / ``geo_temps``: a TEMPERATURE sweep from one scan (``sweep_plan``).  H depends on
+        ``temp`` alone and G on ``geo_temp`` alone, and the logits pass 1 keeps are un-scaled: per
+        ``chunk_size`` slice the queries are encoded and scanned once, ONE ``stats_kept`` call gives the
+        softmax statistics of every temperature from the kept logits, then one pass 2 per semantic and
+        per geographic temperature and a blend + pack per grid point - T + G passes 2 for a T x G x nb
+        grid.  RANGE+: (T, G, nb, B, 1280), a missing list being ``[args.temp]`` / ``[args.geo_temp]``
+        and ``betas=None`` ``[args.beta]``.  RANGE (``temps`` only): (T, B, 1280), row i = ``model(coords)``
+        at ``args.temp = temps[i]`` bit for bit.  H_i runs at the pair (temps[i], 0) and G_j at
+        (12, geo_temps[j]) (beta = 0), so a head's bits do not depend on what else is in the lists:
+        ``out[i, j, b]`` equals ``sweep(coords, betas)[b]`` at ``args.temp = temps[i]``,
+        ``args.geo_temp = geo_temps[j]`` BIT FOR BIT whenever both lie on the same side of 43; when they
+        straddle 43 that call runs both heads' statistics with a running maximum while here only the
+        head above 43 does: equal within the usual bounds.  A slice whose logits were not kept (memory,
+        RANGE_KEEP_LOGITS=0) takes ``scan_stats`` per pair and ``attend``: same bits, slower."""
+        plan = sweep_plan(self.location_model_name, betas, temps, geo_temps, self.args.temp,
+                          getattr(self.args, "geo_temp", None), getattr(self.args, "beta", None),
+                          getattr(self.args, "pv_mode", None))
+        if plan is not None:
+            if self._model_id is None:
+                raise ValueError("sweep() is defined for RANGE / RANGE+ only")
+            return self._temperature_sweep(coords, plan, return_device)
         if self._model_id != _native.MODEL_RANGE_PLUS:
             raise ValueError("sweep() is defined for RANGE+ only")
+        if betas is None:
+            raise TypeError("sweep() needs betas (or temps= / geo_temps= for a temperature sweep)")
         betas = [float(b) for b in betas]
         tau_sem, tau_geo = self._temperatures()
         x = self._coords(coords)
@@ -409,6 +482,33 @@ class LocationEncoder(_EncoderBase):
             H, G = (attend_any(eng, kept, 0, e32, xq, tau_sem, tau_geo, b, st) for b in (1.0, 0.0))
             for j, b in enumerate(betas):
                 out[j, i:i + e64.shape[0]] = eng.finalize(eng.blend(G, H, b), e64)
+        return out if return_device else self._to_host(out)
+
+    def _temperature_sweep(self, coords, plan: SweepPlan, return_device: bool):
+        x = self._coords(coords)
+        B = x.shape[0]
+        out = torch.empty(plan.lead + (B, _native.OUT_DIM), dtype=torch.float64, device=x.device)
+        eng = self.engine
+        T = len(plan.temps)
+        for i in range(0, B, self.chunk_size):
+            e64, e32, xq = eng.encode(x[i:i + self.chunk_size])
+            n = e64.shape[0]
+            eng.scan_stats(e32, xq, *plan.scan_taus, keep_logits=True)
+            kept = eng.kept_queries() == n
+            if kept:
+                stats = eng.stats_kept(0, xq, plan.pairs)          # ONE call for every pair of the grid
+            else:
+                stats = [eng.scan_stats(e32, xq, ts, tg) for ts, tg in plan.pairs]
+            # one pass 2 per semantic temperature (beta = 1) and per geographic one (beta = 0)
+            heads = [attend_any(eng, kept, 0, e32, xq, ts, tg, 1.0 if p < T else 0.0, stats[p])
+                     for p, (ts, tg) in enumerate(plan.pairs)]
+            for ti in range(T):
+                if not plan.geo_temps:                              # RANGE: the semantic retrieval alone
+                    out[ti, i:i + n] = eng.finalize(heads[ti], e64)
+                    continue
+                for gi in range(len(plan.geo_temps)):
+                    for bi, b in enumerate(plan.betas):
+                        out[ti, gi, bi, i:i + n] = eng.finalize(eng.blend(heads[T + gi], heads[ti], b), e64)
         return out if return_device else self._to_host(out)
 
     def _to_host(self, t: torch.Tensor) -> np.ndarray:
@@ -544,20 +644,30 @@ class ShardedLocationEncoder(_EncoderBase):
         return (emb, *tk) if k else emb
 
     @torch.no_grad()
-    def sweep(self, coords, betas, return_device: bool = False, local: bool = False):
-        """(len(betas), B, 1280) float64 for several beta values (BASELINE config "beta sweep")."""
-        if self.location_model_name != "RANGE+":
+    def sweep(self, coords, betas=None, return_device: bool = False, local: bool = False, *, temps=None, geo_temps=None):
+        """(len(betas), B, 1280) float64 for several beta values (BASELINE config "beta sweep").
+        ``temps`` / ``geo_temps``: the temperature sweep of ``LocationEncoder.sweep`` - (T, G, nb, B, 1280)
+        for RANGE+, (T, B, 1280) for RANGE - from one scan per shard (``ShardedRange.sweep``)."""
+        plan = sweep_plan(self.location_model_name, betas, temps, geo_temps, self.args.temp,
+                          getattr(self.args, "geo_temp", None), getattr(self.args, "beta", None),
+                          getattr(self.args, "pv_mode", None))
+        if plan is None and self.location_model_name != "RANGE+":
             raise ValueError("sweep() is defined for RANGE+ only")
+        if plan is None and betas is None:
+            raise TypeError("sweep() needs betas (or temps= / geo_temps= for a temperature sweep)")
         x = self._coords(coords)
         self.sharded.tau_sem, self.sharded.tau_geo = self._temperatures()
+        kw = {} if plan is None else dict(temps=temps, geo_temps=geo_temps)
         if local:
-            out = self.sharded.embed_sweep(x, betas)
+            out = self.sharded.embed_sweep(x, betas, **kw)
             return out if return_device else self._to_host(out)
         B = x.shape[0]
         lo, hi = self._own_rows(B)
-        own = self.sharded.embed_sweep(x[lo:hi], betas)                  # (nb, b_own, 1280)
-        full, flags = self._gather_rows(own.permute(1, 0, 2).contiguous(), B, with_flags=True)
-        full = full.permute(1, 0, 2).contiguous()
+        own = self.sharded.embed_sweep(x[lo:hi], betas, **kw)            # (..., b_own, 1280)
+        lead = tuple(own.shape[:-2])
+        flat = own.reshape((-1,) + tuple(own.shape[-2:]))
+        full, flags = self._gather_rows(flat.permute(1, 0, 2).contiguous(), B, with_flags=True)
+        full = full.permute(1, 0, 2).contiguous().reshape(lead + (B, own.shape[-1]))
         return full.to(self.engine.device) if return_device else self._to_host(full, flags)
 
     def _to_host(self, t: torch.Tensor, flags: Optional[torch.Tensor] = None) -> np.ndarray:
