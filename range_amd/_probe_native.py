@@ -92,24 +92,51 @@ class ProbeEngine:
                              f"{t.dtype} {tuple(t.shape)} on {t.device}")
         return t
 
+    def _ld(self, t: torch.Tensor, name: str) -> int:
+        """Leading dimension of a float64 row-strided 2-d view on the engine device: unit column
+        stride (any when one column wide) and rows that do not overlap."""
+        if t.device != self.device or t.dtype != torch.float64 or t.dim() != 2:
+            raise ValueError(f"{name}: expected a float64 2-d tensor on {self.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        width = t.shape[1]
+        if not t.is_contiguous() and ((width != 1 and t.stride(1) != 1) or t.stride(0) < width):
+            raise ValueError(f"{name}: rows must be unit-stride and must not overlap, got shape "
+                             f"{tuple(t.shape)} with strides {tuple(t.stride())}")
+        return max(t.stride(0), width)
+
+    def _chk_scores(self, P: torch.Tensor, c0: torch.Tensor, rows: int, c: int,
+                    n_alpha: int) -> None:
+        """P (rows, n_alpha*c) and c0 (n_alpha, c) or (n_alpha*c,), contiguous float64."""
+        if tuple(self._chk(P, torch.float64, 2).shape) != (rows, n_alpha * c):
+            raise ValueError(f"scores must have shape ({rows}, {n_alpha * c}), got "
+                             f"{tuple(P.shape)}")
+        if c0.dim() not in (1, 2):
+            raise ValueError(f"intercepts must be 1-d or 2-d, got {tuple(c0.shape)}")
+        if tuple(self._chk(c0, torch.float64, c0.dim()).shape) not in ((n_alpha * c,),
+                                                                        (n_alpha, c)):
+            raise ValueError(f"intercepts must hold {n_alpha} x {c} values, got "
+                             f"{tuple(c0.shape)}")
+
     def empty(self, shape, dtype=torch.float64) -> torch.Tensor:
         return torch.empty(shape, dtype=dtype, device=self.device)
 
     # -- entry points --------------------------------------------------------------------------
     def colstats(self, X: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """Column (min, max, sum) of X (n,d) float64."""
-        self._chk(X, torch.float64, 2)
+        """Column (min, max, sum) of X (n,d) float64, X contiguous or a row-strided view."""
+        ldx = self._ld(X, "colstats")
         n, d = X.shape
         mn, mx, sm = self.empty(d), self.empty(d), self.empty(d)
-        _check(self.lib, self.lib.range_probe_colstats(self._h, X.data_ptr(), n, d, d, _p(mn),
+        _check(self.lib, self.lib.range_probe_colstats(self._h, X.data_ptr(), n, d, ldx, _p(mn),
                                                        _p(mx), _p(sm), self._stream()))
         return mn, mx, sm
 
     def scale_rows(self, X: torch.Tensor, perm: Optional[torch.Tensor] = None,
                    scale: Optional[torch.Tensor] = None, offset: Optional[torch.Tensor] = None,
-                   shift: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Z[i] = (X[perm[i]] * scale + offset) - shift; returns Z (len(perm) or n, d)."""
-        self._chk(X, torch.float64, 2)
+                   shift: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Z[i] = (X[perm[i]] * scale + offset) - shift; returns Z (len(perm) or n, d), written
+        to ``out`` when given.  X and ``out`` may be row-strided views."""
+        ldx = self._ld(X, "scale_rows")
         d = X.shape[1]
         n = X.shape[0] if perm is None else perm.shape[0]
         if perm is not None:
@@ -117,11 +144,14 @@ class ProbeEngine:
         for v in (scale, offset, shift):
             if v is not None and tuple(self._chk(v, torch.float64, 1).shape) != (d,):
                 raise ValueError("per-column vector of the wrong length")
-        Z = self.empty((n, d))
+        Z = self.empty((n, d)) if out is None else out
+        ldz = self._ld(Z, "scale_rows out")
+        if tuple(Z.shape) != (n, d):
+            raise ValueError("out has the wrong shape")
         if n:
             _check(self.lib, self.lib.range_probe_scale_rows(
-                self._h, X.data_ptr(), n, d, d, _p(perm), _p(scale), _p(offset), _p(shift),
-                Z.data_ptr(), d, self._stream()))
+                self._h, X.data_ptr(), n, d, ldx, _p(perm), _p(scale), _p(offset), _p(shift),
+                Z.data_ptr(), ldz, self._stream()))
         return Z
 
     def onehot(self, code: torch.Tensor, c: int, first: int, shift: torch.Tensor) -> torch.Tensor:
@@ -138,9 +168,10 @@ class ProbeEngine:
     def gemm(self, A: torch.Tensor, B: torch.Tensor, trans_a: bool = False, trans_b: bool = False,
              alpha: float = 1.0, beta: float = 0.0, out: Optional[torch.Tensor] = None,
              lower_only: bool = False) -> torch.Tensor:
-        """out = alpha * op(A) @ op(B) + beta * out on the float64 matrix cores."""
-        self._chk(A, torch.float64, 2)
-        self._chk(B, torch.float64, 2)
+        """out = alpha * op(A) @ op(B) + beta * out on the float64 matrix cores; A, B and out
+        may be row-strided views."""
+        lda = self._ld(A, "gemm A")
+        ldb = self._ld(B, "gemm B")
         M, K = (A.shape[1], A.shape[0]) if trans_a else A.shape
         K2, N = (B.shape[1], B.shape[0]) if trans_b else B.shape
         if K != K2:
@@ -149,20 +180,21 @@ class ProbeEngine:
             if beta != 0.0:
                 raise ValueError("beta != 0 needs out")
             out = self.empty((M, N))
-        self._chk(out, torch.float64, 2)
+        ldc = self._ld(out, "gemm out")
         if tuple(out.shape) != (M, N):
             raise ValueError("out has the wrong shape")
         _check(self.lib, self.lib.range_probe_gemm(
-            self._h, int(trans_a), int(trans_b), M, N, K, alpha, A.data_ptr(), A.shape[1],
-            B.data_ptr(), B.shape[1], beta, out.data_ptr(), N, int(lower_only), self._stream()))
+            self._h, int(trans_a), int(trans_b), M, N, K, alpha, A.data_ptr(), lda,
+            B.data_ptr(), ldb, beta, out.data_ptr(), ldc, int(lower_only), self._stream()))
         return out
 
     def gram(self, Z: torch.Tensor, T: torch.Tensor, G: torch.Tensor, B: torch.Tensor,
              zsum: torch.Tensor, tsum: torch.Tensor) -> None:
         """G = Z^T Z (lower), B = Z^T T, column sums of Z and T, for one block of rows; the
-        outputs are preallocated (slices of the per-fold arrays)."""
-        self._chk(Z, torch.float64, 2)
-        self._chk(T, torch.float64, 2)
+        outputs are preallocated (slices of the per-fold arrays).  Z and T may be row-strided
+        views."""
+        ldz = self._ld(Z, "gram Z")
+        ldt = self._ld(T, "gram T")
         rows, d = Z.shape
         c = T.shape[1]
         if T.shape[0] != rows or tuple(G.shape) != (d, d) or tuple(B.shape) != (d, c) or \
@@ -171,8 +203,8 @@ class ProbeEngine:
         for t in (G, B, zsum, tsum):
             if not t.is_contiguous() or t.dtype != torch.float64 or t.device != self.device:
                 raise ValueError("gram: outputs must be contiguous float64 on the engine device")
-        _check(self.lib, self.lib.range_probe_gram(self._h, Z.data_ptr(), d, T.data_ptr(), c, rows,
-                                                   d, c, G.data_ptr(), B.data_ptr(),
+        _check(self.lib, self.lib.range_probe_gram(self._h, Z.data_ptr(), ldz, T.data_ptr(), ldt,
+                                                   rows, d, c, G.data_ptr(), B.data_ptr(),
                                                    zsum.data_ptr(), tsum.data_ptr(),
                                                    self._stream()))
 
@@ -209,7 +241,11 @@ class ProbeEngine:
     def r2_sums(self, P: torch.Tensor, c0: torch.Tensor, T: torch.Tensor, tsum: torch.Tensor,
                 n_alpha: int) -> torch.Tensor:
         """(n_alpha, c, 2): residual and total sums of squares per alpha and target."""
+        self._chk(T, torch.float64, 2)
         rows, c = T.shape
+        self._chk_scores(P, c0, rows, c, n_alpha)
+        if tuple(self._chk(tsum, torch.float64, 1).shape) != (c,):
+            raise ValueError(f"r2_sums: tsum must have shape ({c},), got {tuple(tsum.shape)}")
         out = self.empty((n_alpha, c, 2))
         _check(self.lib, self.lib.range_probe_r2_sums(self._h, P.data_ptr(), c0.data_ptr(),
                                                       T.data_ptr(), rows, c, n_alpha,
@@ -221,6 +257,10 @@ class ProbeEngine:
                  n_cls: int, present: Optional[torch.Tensor]) -> torch.Tensor:
         """(n_alpha,) int64 counts of correctly classified rows."""
         self._chk(code, torch.int32, 1)
+        self._chk_scores(P, c0, code.shape[0], c, n_alpha)
+        if present is not None and tuple(self._chk(present, torch.int32, 1).shape) != (n_cls,):
+            raise ValueError(f"accuracy: present must have shape ({n_cls},), got "
+                             f"{tuple(present.shape)}")
         hits = torch.zeros(n_alpha, dtype=torch.int64, device=self.device)
         _check(self.lib, self.lib.range_probe_accuracy(self._h, P.data_ptr(), c0.data_ptr(),
                                                        code.data_ptr(), code.shape[0], c, n_alpha,
