@@ -1,6 +1,7 @@
 /*
  * range_hip.h - C ABI of librange_hip.so: the MI355X (gfx950) engine behind
- * range_amd.load_model(...)(locs), the drop-in for the RANGE / RANGE+ forward path of mvrl/RANGE.
+ * range_amd.load_model(...)(locs), the drop-in for the RANGE / RANGE+ forward path of mvrl/RANGE
+ * and for its training-free encoders (range_coord_features, range_posenc_features).
  *
  * The reference is pure Python / PyTorch and has NO plugin, operator or FFI layer for this path
  * (SURVEY.md section 8(b)); the "interface each entry point replaces" is therefore a span of the
@@ -175,6 +176,38 @@ int range_encode_raw(range_ctx* ctx, const double* lonlat_dev, int64_t B, double
 #define RANGE_COORD_WRAP 2
 int range_coord_features(range_ctx* ctx, int32_t mode, const double* lonlat_dev, int64_t B,
                          double* out_dev, range_stream_t stream);
+
+/* The reference's training-free positional encoders (load_model names 'Theory' and 's2vec_grid',
+ * 's2vec_spherec', 's2vec_spherecplus', 's2vec_spherem', 's2vec_spheremplus'; range/range.py:164-168,
+ * :176-188, :269-275; positional_encoding/theory.py:55-90, sphere2vec/sphere2vec.py:95-248 - numpy on the
+ * host there).  float64; the coordinates are (lon,lat) DEGREES used as radians, as the reference does.
+ * With x = lon, y = lat, f = freq[i], al = x f, at = y f, S = sin, C = cos, a row of F * P doubles is
+ *   THEORY      P = 6   out[6i + j]: S, C of a1 f | S, C of a2 f | S, C of a3 f;  a1 = x*1 + y*0,
+ *                       a2 = x*(-1/2) + y*(sqrt(3)/2), a3 = x*(-1/2) + y*(-sqrt(3)/2) (products and sum rounded
+ *                       separately)
+ *   GRID        P = 4   out[2i + r] = S | C (al);  out[2F + 2i + r] = S | C (at)
+ *   the sphere kinds, T terms each written twice: out[i 2T + 2t + r], r = 0, 1
+ *   SPHEREC     P = 6   S(at), C(at) C(al), C(at) S(al)
+ *   SPHERECPLUS P = 12  S(at), C(at), S(al), C(al), C(at) C(al), C(at) S(al)
+ *   SPHEREM     P = 10  S(at), C(at) C(x), C(y) C(al), C(at) S(x), C(y) S(al)
+ *   SPHEREMPLUS P = 16  S(at), C(at), S(al), C(al), then SPHEREM's last four
+ *   freq_host  : F float64 frequencies, HOST memory, 1 <= F <= RANGE_POSENC_MAX_F (the reference's tables:
+ *                range_amd/posenc.py).  The context keeps a device copy of every table it has seen: the
+ *                first call with a table allocates and uploads synchronously, later calls launch only.
+ *   lonlat_dev : (B,2) float64;  out_dev : (B, range_posenc_width(kind, F)) float64, 16-byte aligned.
+ * A NaN / infinite coordinate gives NaN where the reference's numpy does.  Any B >= 1 (64-bit indexing,
+ * the launch walks its tiles).  RANGE_ERR_INVALID: a null pointer, B <= 0, F out of range, an unknown
+ * kind, a misaligned out_dev.  range_posenc_width: the row width F * P, 0 for a bad kind or F. */
+#define RANGE_POSENC_THEORY 0
+#define RANGE_POSENC_GRID 1
+#define RANGE_POSENC_SPHEREC 2
+#define RANGE_POSENC_SPHERECPLUS 3
+#define RANGE_POSENC_SPHEREM 4
+#define RANGE_POSENC_SPHEREMPLUS 5
+#define RANGE_POSENC_MAX_F 64
+int32_t range_posenc_width(int32_t kind, int32_t F);
+int range_posenc_features(range_ctx* ctx, int32_t kind, const double* freq_host, int32_t F,
+                          const double* lonlat_dev, int64_t B, double* out_dev, range_stream_t stream);
 
 /* Kernel B, pass 1.  Streaming log-sum-exp statistics of the temperature-scaled logits of
  * range/range.py:213-215 (semantic) and :231-234 (geographic) over THIS ctx's bank rows.

@@ -39,6 +39,7 @@ SYMBOLS = (
     "range_set_pv_mode", "range_get_pv_mode", "range_set_keys", "range_debug_raise_async_error",
     "range_scan_stats_at", "range_p1_splits", "range_check_async_error", "range_stream_read_timed",
     "range_async_error_flag", "range_topk_last", "range_set_temperatures", "range_stats_kept",
+    "range_posenc_width", "range_posenc_features",
 )
 PV_MODES = {"exact": 0, "bf16x3": 1}   # range_set_pv_mode
 
@@ -110,6 +111,9 @@ def load_library() -> C.CDLL:
     lib.range_topk_stream_timed.argtypes = [vp, vp, i64, i32, vp, vp, i32, C.POINTER(f32), vp]
     lib.range_stream_read_timed.argtypes = [vp, i32, i32, i32, C.POINTER(f32), vp]
     lib.range_coord_features.argtypes = [vp, i32, vp, i64, vp, vp]
+    lib.range_posenc_width.argtypes = [i32, i32]
+    lib.range_posenc_width.restype = i32
+    lib.range_posenc_features.argtypes = [vp, i32, vp, i32, vp, i64, vp, vp]
     lib.range_set_pv_mode.argtypes = [vp, i32]
     lib.range_get_pv_mode.argtypes = [vp]
     lib.range_get_pv_mode.restype = i32
@@ -327,6 +331,30 @@ class HipEngine:
         out = self._empty((B, COORD_DIMS[mode]), torch.float64)
         _check(self.lib, self.lib.range_coord_features(self._h, mode, lonlat.data_ptr(), B,
                                                        out.data_ptr(), self._stream()))
+        return out
+
+    def posenc_features(self, lonlat: torch.Tensor, kind: int, freq: np.ndarray,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The training-free positional encoders 'Theory' / 's2vec_*' (range_posenc_features): ``lonlat``
+        (B,2) float64 degrees, ``kind`` a ``range_amd.posenc.KIND_*``, ``freq`` the (F,) float64 frequency
+        table (host) -> (B, width) float64.  ``out``: a contiguous (B, width) float64 view to write into."""
+        self._t(lonlat, torch.float64, (2,))
+        B = lonlat.shape[0]
+        freq = np.ascontiguousarray(freq, dtype=np.float64)
+        if freq.ndim != 1:
+            raise ValueError(f"freq must be one-dimensional, got {freq.shape}")
+        F = freq.shape[0]
+        width = self.lib.range_posenc_width(kind, F)
+        if width <= 0:
+            raise ValueError(f"positional encoder kind {kind} with {F} frequencies")
+        if out is None:
+            out = self._empty((B, width), torch.float64)
+        else:
+            self._t(out, torch.float64, (width,))
+            if out.shape[0] != B:
+                raise ValueError(f"out has {out.shape[0]} rows for {B} locations")
+        _check(self.lib, self.lib.range_posenc_features(self._h, kind, freq.ctypes.data, F, lonlat.data_ptr(), B,
+                                                        out.data_ptr(), self._stream()))
         return out
 
     def blend(self, G: torch.Tensor, H: torch.Tensor, beta: float) -> torch.Tensor:

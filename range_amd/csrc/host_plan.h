@@ -607,4 +607,48 @@ inline SmallPlan plan_forward_small(int n_cu, int64_t n_rows, int64_t B, const P
     return p;
 }
 
+// The training-free positional encoders (posenc_kernel.h; range_posenc_features).  Kinds, and the
+// outputs one frequency contributes to a row: Theory 6 (sin, cos of three angles), grid 4 (sin, cos of
+// lon and of lat), the sphere kinds 2T - T terms, each written twice.
+enum { PE_THEORY = 0, PE_GRID = 1, PE_SPHEREC = 2, PE_SPHERECPLUS = 3, PE_SPHEREM = 4, PE_SPHEREMPLUS = 5,
+       PE_KINDS = 6 };
+constexpr int POSENC_BLOCK = 256;                  // work items (location, frequency) of a tile = threads of a workgroup
+constexpr int POSENC_MAX_F = 64;
+constexpr int64_t POSENC_MAX_GRID = 1 << 20;       // workgroups of a launch; more tiles are walked grid-stride
+RANGE_HD constexpr int posenc_per_freq(int kind) {
+    return kind == PE_THEORY ? 6 : kind == PE_GRID ? 4 : kind == PE_SPHEREC ? 6 : kind == PE_SPHERECPLUS ? 12
+         : kind == PE_SPHEREM ? 10 : kind == PE_SPHEREMPLUS ? 16 : 0;
+}
+
+struct PosencPlan {
+    bool valid = false;
+    int per_freq = 0, width = 0;        // outputs per frequency; row width = F * per_freq
+    int64_t items = 0, n_tiles = 0;     // B * F work items in tiles of POSENC_BLOCK
+    unsigned grid = 0;
+    int block = POSENC_BLOCK;
+    bool staged = false;                // the tile's outputs go through LDS and are written out linearly (all kinds but grid)
+    int locs_per_tile = 0;              // spherem / spheremplus: most locations a tile touches
+    size_t lds_bytes = 0;
+    // tiles workgroup `blk` walks: blk, blk + grid, ... below n_tiles
+    int64_t tiles_of(int64_t blk) const { return blk < n_tiles ? (n_tiles - blk + grid - 1) / grid : 0; }
+};
+
+// Invalid: unknown kind, F outside 1 .. POSENC_MAX_F, B < 1, or an output of more than 2^62 bytes.
+inline PosencPlan posenc_plan(int kind, int F, int64_t B) {
+    PosencPlan p;
+    p.per_freq = posenc_per_freq(kind);
+    if (!p.per_freq || F < 1 || F > POSENC_MAX_F || B < 1) return p;
+    p.width = F * p.per_freq;
+    if (B > (INT64_C(1) << 59) / p.width) return p;
+    p.items = B * F;
+    p.n_tiles = (p.items + POSENC_BLOCK - 1) / POSENC_BLOCK;
+    p.grid = (unsigned)std::min(p.n_tiles, POSENC_MAX_GRID);
+    p.staged = kind != PE_GRID;
+    if (kind == PE_SPHEREM || kind == PE_SPHEREMPLUS)
+        p.locs_per_tile = (F - 1 + POSENC_BLOCK - 1) / F + 1;     // a tile may start at frequency F - 1 of a location
+    p.lds_bytes = ((p.staged ? (size_t)POSENC_BLOCK * p.per_freq : 0) + (size_t)3 * p.locs_per_tile) * sizeof(double);
+    p.valid = true;
+    return p;
+}
+
 }  // namespace range_host

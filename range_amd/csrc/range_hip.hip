@@ -27,6 +27,7 @@
 #include "attend_bf16x3.h"
 #include "attend_small.h"
 #include "encoder_kernel.h"
+#include "posenc_kernel.h"
 
 using namespace range_hip;
 using namespace range_host;
@@ -131,6 +132,12 @@ struct range_ctx {
         DevBuf<uint2> ws_tg_cand;                // candidate lists: lengths (B, lists), rows (B, lists, TG_CAP_L); overflow flags (B)
         DevBuf<uint32_t> ws_read_sink;           // range_stream_read_timed: one word per workgroup
     } topk;
+    // range_posenc_features: the frequency tables seen so far, each in device memory of its own (a table
+    // is never overwritten: a launch in flight on another stream may still read it)
+    struct Posenc {
+        struct Table { std::vector<double> host; DevBuf<double> dev; };
+        std::vector<std::unique_ptr<Table>> tables;
+    } posenc;
     // words of host memory the kernels can write (hipHostMallocMapped; async_err.h): set by a persistent
     // kernel whose bounded wait for other workgroups gave up; read - without synchronising - by the
     // next call and behind every synchronising exit (check_async_error)
@@ -1621,6 +1628,67 @@ int range_last_attend_geometry(const range_ctx* c, int32_t* n_query_tiles, int32
     if (n_query_tiles) *n_query_tiles = c->pass.last_qtiles;
     if (n_splits) *n_splits = c->pass.last_splits;
     return RANGE_OK;
+}
+
+}  // extern "C"
+
+// the positional encoders (posenc_kernel.h), by kind
+static void (*posenc_kernel_for(int kind))(PosencArgs) {
+    static void (*const posenc_kernels[PE_KINDS])(PosencArgs) = {
+        posenc_features_kernel<PE_THEORY>, posenc_features_kernel<PE_GRID>, posenc_features_kernel<PE_SPHEREC>,
+        posenc_features_kernel<PE_SPHERECPLUS>, posenc_features_kernel<PE_SPHEREM>, posenc_features_kernel<PE_SPHEREMPLUS>};
+    return posenc_kernels[kind];
+}
+
+// The device copy of a frequency table: the context keeps every table it has seen (a model has one; at
+// most POSENC_TABLES_MAX, beyond which the device is drained and the tables are dropped).  A new table
+// costs one allocation and a synchronous upload; a known one nothing.
+constexpr size_t POSENC_TABLES_MAX = 64;
+static int posenc_table(range_ctx* c, const double* freq_host, int32_t F, const double** dev) {
+    auto& tables = c->posenc.tables;
+    for (auto& t : tables)
+        if ((int32_t)t->host.size() == F && std::memcmp(t->host.data(), freq_host, (size_t)F * sizeof(double)) == 0) {
+            *dev = t->dev.p;
+            return RANGE_OK;
+        }
+    if (tables.size() >= POSENC_TABLES_MAX) {
+        HIP_TRY(hipDeviceSynchronize());
+        tables.clear();
+    }
+    auto t = std::make_unique<range_ctx::Posenc::Table>();
+    t->host.assign(freq_host, freq_host + F);
+    HIP_TRY(t->dev.upload(t->host));
+    *dev = t->dev.p;
+    tables.push_back(std::move(t));
+    return RANGE_OK;
+}
+
+extern "C" {
+
+int32_t range_posenc_width(int32_t kind, int32_t F) {
+    if (F < 1 || F > POSENC_MAX_F) return 0;
+    return posenc_per_freq(kind) * F;
+}
+
+int range_posenc_features(range_ctx* c, int32_t kind, const double* freq_host, int32_t F, const double* lonlat,
+                          int64_t B, double* out, range_stream_t stream) {
+    if (!c || !freq_host || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
+    if (kind < 0 || kind >= PE_KINDS) return fail(RANGE_ERR_INVALID, "positional encoder kind %d", kind);
+    if (F < 1 || F > POSENC_MAX_F) return fail(RANGE_ERR_INVALID, "F = %d frequencies (1 .. %d)", F, POSENC_MAX_F);
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(RANGE_ERR_INVALID, "out_dev must be 16-byte aligned");
+    const PosencPlan p = posenc_plan(kind, F, B);
+    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld locations: output too large", (long long)B);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    PosencArgs a{};
+    if (int rc = posenc_table(c, freq_host, F, &a.freq)) return rc;
+    a.lonlat = lonlat;
+    a.out = out;
+    a.B = B;
+    a.n_tiles = p.n_tiles;
+    a.F = F;
+    return launch(posenc_kernel_for(kind), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

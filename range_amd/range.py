@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _native
+from . import _native, posenc
 from ._hostpool import POOL
 from .bank import PreparedBank
 from .bankfile import load_any as load_bank
@@ -278,6 +278,43 @@ class _CoordLocationModel(nn.Module):
         return eng.coord_features(x, _native.COORD_WRAP) if x.shape[0] else torch.empty((0, 4), dtype=torch.float64, device=x.device)
 
 
+class PosencLocationModel(nn.Module):
+    """``loc_model`` of 'Theory' (``Theory(frequency_num=32, min_radius=1)``, range.py:167) and of the
+    's2vec_*' names (``get_sphere2vec(name=...)``, :180): parameter-free modules there too, with the same
+    read-only attributes - ``frequency_num``, ``min_radius``, ``max_radius``, ``freq_list``,
+    ``embedding_dim``, and ``name`` for the s2vec kinds.  The call maps (B,2) (lon,lat) degrees to the
+    (B, embedding_dim) encoding in the coordinates' dtype, a tensor on the engine's GPU (the reference
+    computes it with numpy on the host, in float64 whatever the dtype, and converts back)."""
+
+    def __init__(self, engine, model_name: str):
+        super().__init__()
+        s = posenc.spec(model_name)
+        self._engine, self._kind = [engine], s.kind
+        self.frequency_num, self.min_radius, self.max_radius = s.frequency_num, s.min_radius, s.max_radius
+        self.freq_list = posenc.freq_list(model_name)
+        self.freq_list.setflags(write=False)
+        self.embedding_dim = s.width
+        if model_name != "Theory":
+            self.name = model_name.split("_")[-1]                         # range.py:179
+
+    @staticmethod
+    def result_dtype(coords) -> torch.dtype:
+        """The reference converts its float64 result to the coordinates' dtype (theory.py:90,
+        sphere2vec.py:248); anything that is not a floating-point tensor / array counts as float64."""
+        dt = coords.dtype if torch.is_tensor(coords) else torch.as_tensor(np.asarray(coords)).dtype
+        return dt if dt.is_floating_point else torch.float64
+
+    @torch.no_grad()
+    def forward(self, coords):
+        return self.encode(_as_coords(coords, self._engine[0].device), self.result_dtype(coords))
+
+    def encode(self, x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        """``x``: (B,2) float64 on the engine's GPU (the coordinates widened) -> (B, embedding_dim) ``dtype``."""
+        if x.shape[0] == 0:
+            return torch.empty((0, self.embedding_dim), dtype=dtype, device=x.device)
+        return self._engine[0].posenc_features(x, self._kind, self.freq_list).to(dtype)
+
+
 class _EncoderBase(nn.Module):
     """What the one-GPU and the row-sharded encoder share: ``args``, ``engine``, ``loc_model``."""
 
@@ -369,10 +406,23 @@ class LocationEncoder(_EncoderBase):
             self._device = _device_of(args.device)
             self.engine = _native.HipEngine(self._device)
             self.loc_model = _CoordLocationModel(self.engine, mode)
+        elif posenc.is_posenc_name(self.location_model_name):           # range.py:164-168, 176-188
+            # (an unknown s2vec kind: NotImplementedError here; the reference's get_sphere2vec returns
+            # None for it and the failure comes at the first call)
+            spec = posenc.spec(self.location_model_name)
+            print("Using Theory" if self.location_model_name == "Theory" else "Using sphere2vec")
+            # the TRUE row width: the reference leaves 0 (Theory, the sphere kinds) or nothing (grid)
+            # here and never reads it; the batch driver sizes its staging buffers from it
+            self.location_feature_dim = spec.width
+            self._model_id = None
+            self._device = _device_of(args.device)
+            self.engine = _native.HipEngine(self._device)
+            self.loc_model = PosencLocationModel(self.engine, self.location_model_name)
+            self._posenc = spec
         else:
-            # the reference dispatches more encoder families here (GeoCLIP, CSP, SINR, TaxaBind,
-            # Theory, sphere2vec; range.py:124-198): third-party pretrained baselines, out of
-            # scope for this engine
+            # the reference dispatches more encoder families here (GeoCLIP, TaxaBind, CSP, SINR;
+            # range.py:124-150, 190-197): third-party pretrained baselines that need their own
+            # packages and checkpoints, out of scope for this engine
             raise NotImplementedError(f"{self.location_model_name} not implemented")
         self._freeze()
 
@@ -392,6 +442,9 @@ class LocationEncoder(_EncoderBase):
         B = x.shape[0]
         if return_topk is not None:
             return self._forward_chunks(x, return_device, _topk_arg(return_topk, self._model_id is not None))
+        if getattr(self, "_posenc", None) is not None:
+            # Theory / s2vec_*: a device tensor of the coordinates' dtype (range.py:269-275)
+            return self.loc_model.encode(x, self.loc_model.result_dtype(coords))
         if getattr(self, "_coord_mode", None) is not None:
             # Direct / Wrap return a device tensor, Cartesian_3D a host ndarray (its rad_to_cart
             # runs in numpy, range.py:265-268)

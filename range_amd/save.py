@@ -67,15 +67,19 @@ class EmbeddingPipeline:
     @torch.no_grad()
     def run(self, batches: Iterable) -> Iterator[np.ndarray]:
         """``batches`` yields (B,2) coordinate tensors/arrays.  Yields one float64 ndarray
-        (B,1280) per batch, in order.  Each yielded array is a fresh host array."""
-        if getattr(self.model, "_model_id", None) is None:
+        (B,1280) per batch, in order.  Each yielded array is a fresh host array.  (Theory / s2vec_*:
+        (B, location_feature_dim) in the coordinates' dtype, what ``model(coords)`` gives.)"""
+        pe = getattr(self.model, "_posenc", None)
+        if getattr(self.model, "_model_id", None) is None and pe is None:
             # SatCLIP and the training-free coordinate encoders: tiny outputs, no pipeline -
             # one call per batch like range/utils/save.py:28-30
             for coords in batches:
                 out = self.model(coords)
                 yield out.cpu().numpy() if torch.is_tensor(out) else np.asarray(out)
             return
-        inflight: List[Tuple[int, int]] = []          # (slot, rows)
+        # Theory / s2vec_* (rows of 1.5 - 4 KB float64) take the same pipeline as RANGE / RANGE+: the
+        # kernel writes into the slot's device buffer, the copy stream drains it under the next batch
+        inflight: List[Tuple[int, int, Optional[np.dtype]]] = []      # (slot, rows, dtype of the result or None: float64)
         compute = torch.cuda.current_stream(self.device)
         i = 0
         for coords in batches:
@@ -85,21 +89,29 @@ class EmbeddingPipeline:
             x = self._coords_async(slot, coords)
             n = x.shape[0]
             pinned, dev = self._buffers(slot, n)
-            beta = 1.0 if self.model._model_id == 0 else float(self.model.args.beta)
-            for lo in range(0, n, self.model.chunk_size):
-                self.engine.forward(x[lo:lo + self.model.chunk_size], self.model._model_id, beta,
-                                    out=dev[lo:lo + self.model.chunk_size])
+            dtype = None
+            if pe is not None:
+                if n:
+                    self.engine.posenc_features(x, pe.kind, self.model.loc_model.freq_list, out=dev)
+                # the result has the coordinates' dtype, as model(coords): rounded on the host, like .to(dtype)
+                rd = self.model.loc_model.result_dtype(coords)
+                dtype = None if rd == torch.float64 else torch.empty((), dtype=rd).numpy().dtype
+            else:
+                beta = 1.0 if self.model._model_id == 0 else float(self.model.args.beta)
+                for lo in range(0, n, self.model.chunk_size):
+                    self.engine.forward(x[lo:lo + self.model.chunk_size], self.model._model_id, beta,
+                                        out=dev[lo:lo + self.model.chunk_size])
             self._done[slot].record(compute)
             with torch.cuda.stream(self.copy_stream):
                 self.copy_stream.wait_event(self._done[slot])
                 pinned.copy_(dev, non_blocking=True)
                 self._copied[slot].record(self.copy_stream)
-            inflight.append((slot, n))
+            inflight.append((slot, n, dtype))
             i += 1
         while inflight:
             yield self._collect(*inflight.pop(0))
 
-    def _collect(self, slot: int, n: int) -> np.ndarray:
+    def _collect(self, slot: int, n: int, dtype=None) -> np.ndarray:
         self._copied[slot].synchronize()
         self.engine.check_async_error()       # (a persistent launch of this batch that gave up: NaN rows, known now)
         # a fresh array per batch (the reference's contract); its first-touch page faults are
@@ -107,7 +119,7 @@ class EmbeddingPipeline:
         src = self._pinned[slot][:n].numpy()
         out = POOL.take(*src.shape)
         self.engine.host_copy(out, src)
-        return out
+        return out if dtype is None else out.astype(dtype)
 
 
 class ShardedEmbeddingPipeline:
