@@ -9,35 +9,18 @@ rounds away at every addition.  A correct kernel returns the expectation bit for
 summation order; a dropped, doubled or misplaced row, block, part or query changes the result by at
 least one in-class term.  Every check here is ``torch.equal``.
 """
-import contextlib
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from range_amd import _native, load_model
+from exact_helpers import DEV, _assert_equal, _assert_rows, _dev, _env, _fwd_queries, _fwd_want, _model
+from range_amd import _native
 from tools import exact_bank as X
-from tools import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 TAU = X.TAU
-
-
-@contextlib.contextmanager
-def _env(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    os.environ.update({k: str(v) for k, v in kv.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,19 +50,6 @@ def _release_engines():
         e.close()
     _ENGINES.clear()
     torch.cuda.empty_cache()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _assert_equal(got, want, what):
-    if torch.equal(got, want):
-        return
-    bad = (got != want).any(dim=1) if got.dim() == 2 else (got != want)
-    rows = torch.nonzero(bad).flatten().tolist()
-    d = float((got.double() - want.double()).abs().max())
-    raise AssertionError(f"{what}: {len(rows)} of {got.shape[0]} rows differ (first {rows[:8]}), max |diff| {d:.3e}")
 
 
 def _check_stats(st, bank, q, geo, what):
@@ -291,45 +261,6 @@ def test_topk_brute_force_fallback_exact():
 
 
 # -- forward level: production temperatures, constant-e-hat encoder ------------------------------
-L_ENC, H_ENC = 10, 64
-
-
-def _model(tmp_path, bank, c, model, beta):
-    """load_model from a checkpoint whose last layer is weight 0, bias e-hat of class c, and an
-    .npz bank at axis locations."""
-    w = synth.make_encoder_weights(L_ENC, H_ENC, 256, 2, 5)
-    w["last_layer.weight"][:] = 0.0
-    w["last_layer.bias"][:] = X.direction_vector(int(bank.sem_dir[c]))
-    sd = {}
-    for key, v in w.items():
-        t = torch.from_numpy(np.ascontiguousarray(v))
-        sd[f"model.location.nnet.{key}"] = t
-        sd[f"model.nnet.{key}"] = t
-    ck = str(tmp_path / "const.ckpt")
-    torch.save({"hyper_parameters": synth.default_hparams(L_ENC, H_ENC, 256, 2), "state_dict": sd}, ck)
-    db = str(tmp_path / "db.npz")
-    np.savez(db, locs=X.lonlat_of(bank.geo), image_embeddings=bank.values, satclip_embeddings=bank.keys)
-    return load_model(model, pretrained_path=ck, device=DEV, db_path=db, beta=beta)
-
-
-def _fwd_queries(bank, c, B, seed):
-    rng = np.random.default_rng(seed)
-    axes = np.flatnonzero(bank.geo_size[:X.N_GEO_QUERIED] > 0)
-    geo = np.concatenate([axes, rng.choice(axes, B)])[:B]
-    q = X.Queries(np.full(B, c), geo, np.tile(X.direction_vector(int(bank.sem_dir[c])), (B, 1)), None)
-    return q, X.lonlat_of(geo)
-
-
-def _fwd_want(bank, q, beta, geo):
-    e = q.e32[:1].astype(np.float64).repeat(len(q.sem), 0)
-    return np.concatenate([X.expect(bank, q, beta, geo).astype(np.float64), e], axis=1)
-
-
-def _assert_rows(got, want, what):
-    got = torch.as_tensor(got).cpu()
-    _assert_equal(got, torch.from_numpy(want), what)
-
-
 @pytest.mark.parametrize("B", [17, 700, 4100])
 def test_forward_geo_head_only(tmp_path, B):
     """RANGE+ beta = 0 on a ragged bank: the geographic head alone (tau 40), one-pass path (B <= 32),
