@@ -1,5 +1,6 @@
-// Primitives every kernel header of the RANGE engine builds on: tile constants, the inline-asm MFMA /
-// LDS-DMA statements with the hazards each guards against, lane swaps, the merge of two statistics.
+// Primitives every kernel header of the RANGE engine builds on: tile constants, the packed 16-bit
+// conversions and bf16 planes, the inline-asm MFMA / LDS-DMA statements with the hazards each guards
+// against, lane swaps, the merge of two statistics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +12,8 @@ namespace range_hip {
 using range_host::part_begin;       // (host_plan.h: the partition arithmetic, also run under sanitizers on the CPU)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int KEY_DIM = 256;
 constexpr int VAL_DIM = 1024;
@@ -32,6 +35,29 @@ template <class T>
 __device__ __forceinline__ void lane_rows(T (&prow)[4], int g) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) prow[r] = (T)pi_row(4 * g + r);
+}
+
+// round-to-nearest-even float32 -> bf16 of two values, packed (lo = a, hi = b)
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
+    uint32_t r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// two floats -> packed fp16, round to nearest even: gfx950's v_cvt_pk_f16_f32 (bitwise the (_Float16) cast
+// on 2^24 pairs incl. exact ties and subnormal results: tools/micro/cvt_pk_f16_rne.hip)
+__device__ __forceinline__ uint32_t cvt_pk_f16(float a, float b) {
+    uint32_t r;
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// the two leading bf16 planes of a pair of floats, packed like cvt_pk_bf16 (x = x_h + x_m to 2^-17),
+// and what the two leave (ra, rb)
+__device__ __forceinline__ void split2(float a, float b, uint32_t& h, uint32_t& m, float& ra, float& rb) {
+    h = cvt_pk_bf16(a, b);
+    const float ha = a - __uint_as_float(h << 16), hb = b - __uint_as_float(h & 0xFFFF0000u);
+    m = cvt_pk_bf16(ha, hb);
+    ra = ha - __uint_as_float(m << 16);
+    rb = hb - __uint_as_float(m & 0xFFFF0000u);
 }
 
 // f32 MFMA with the accumulator pinned to arch VGPRs (inline asm).  Why not the builtin: with a

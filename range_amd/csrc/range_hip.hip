@@ -561,7 +561,7 @@ static int upload_keys(range_ctx* c, const float* keys, int64_t n_rows, int64_t 
     HIP_TRY(c->bank.d_keys_bf16.ensure((size_t)n_tiles * (TSB_TILE_BYTES / 4)));
     const int64_t threads = n_tiles * 8 * 64;
     if (int lrc = launch(keyfrag_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, c->bank.d_keys.p,
-                       n_pad, n_tiles, reinterpret_cast<ts_u32x4*>(c->bank.d_keys_bf16.p))) return lrc;
+                       n_pad, n_tiles, reinterpret_cast<u32x4*>(c->bank.d_keys_bf16.p))) return lrc;
     if (!c->topk.ws_topk_sync.p) {
         HIP_TRY(c->topk.ws_topk_sync.ensure(TOPKS_SYNC_WORDS));
         HIP_TRY(hipMemset(c->topk.ws_topk_sync.p, 0, TOPKS_SYNC_WORDS * 4));
@@ -970,7 +970,7 @@ static int topk_gemm_route(range_ctx* c, const TopkPlan& p, const float* ehat32,
         HIP_TRY(c->bank.d_keys_f16.ensure((size_t)n_tiles * (TSB_TILE_BYTES / 4)));
         const int64_t threads = n_tiles * 8 * 64;
         int rc = launch(keyfrag_f16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, c->bank.d_keys.p,
-                        c->bank.n_pad, n_tiles, ks, reinterpret_cast<ts_u32x4*>(c->bank.d_keys_f16.p));
+                        c->bank.n_pad, n_tiles, ks, reinterpret_cast<u32x4*>(c->bank.d_keys_f16.p));
         if (rc) return rc;
         c->bank.tg_key_scale = ks;
     }
@@ -1006,7 +1006,7 @@ static int topk_gemm_route(range_ctx* c, const TopkPlan& p, const float* ehat32,
         {
             ProfScope ps(c, RANGE_PROF_TOPK_STREAM, s);
             if (int lrc = launch(qfrag_f16_kernel, dim3((unsigned)p.n_groups), dim3(256), 0, s, ehat32, B,
-                                 reinterpret_cast<ts_u32x4*>(c->topk.ws_tg_qfrag.p), c->topk.ws_tg_qscale.p))
+                                 reinterpret_cast<u32x4*>(c->topk.ws_tg_qfrag.p), c->topk.ws_tg_qscale.p))
                 return lrc;
             ga.tile_stride = p.tile_stride;
             if (int lrc = launch(topk_gemm_kernel<0>, ggrid, gblock, TG_LDS_BYTES, s, ga)) return lrc;
@@ -1118,14 +1118,14 @@ int range_topk_stream_timed(range_ctx* c, const float* ehat32, int64_t B, int32_
 // chip, measured the same way as range_topk_stream_timed.  16-byte non-temporal loads, 8 in flight
 // per thread, 1 024 workgroups; the xor of everything read goes to one word per workgroup so that
 // the loads stay.
-__global__ __launch_bounds__(256) void stream_read_kernel(const ts_u32x4* __restrict__ p, int64_t n16, int passes,
+__global__ __launch_bounds__(256) void stream_read_kernel(const u32x4* __restrict__ p, int64_t n16, int passes,
                                                           uint32_t* __restrict__ sink) {
     // a workgroup reads 32 KB contiguous per step (8 loads of 16 bytes per thread, 4 KB apart)
     const int64_t step = (int64_t)gridDim.x * 2048;
-    ts_u32x4 acc = {0u, 0u, 0u, 0u};
+    u32x4 acc = {0u, 0u, 0u, 0u};
     for (int ps = 0; ps < passes; ++ps) {
         for (int64_t base = (int64_t)blockIdx.x * 2048; base < n16; base += step) {
-            ts_u32x4 v[8];
+            u32x4 v[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int64_t i = base + u * 256 + threadIdx.x;
@@ -1150,7 +1150,7 @@ int range_stream_read_timed(range_ctx* c, int32_t f32_keys, int32_t passes, int3
     if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_tiles = c->bank.n_pad / BLK;
-    const ts_u32x4* src = f32_keys ? reinterpret_cast<const ts_u32x4*>(c->bank.d_keys.p) : reinterpret_cast<const ts_u32x4*>(c->bank.d_keys_bf16.p);
+    const u32x4* src = f32_keys ? reinterpret_cast<const u32x4*>(c->bank.d_keys.p) : reinterpret_cast<const u32x4*>(c->bank.d_keys_bf16.p);
     const int64_t n16 = f32_keys ? c->bank.n_pad * (KEY_DIM * 4 / 16) : n_tiles * (TSB_TILE_BYTES / 16);
     const int grid = 4 * c->n_cu;
     HIP_TRY(c->topk.ws_read_sink.ensure((size_t)grid));

@@ -72,13 +72,62 @@ constexpr int TG_CAP_X = 256;                // candidates whose float32 similar
 constexpr float TG_EPS_REL = 0.00105f;
 typedef _Float16 ts_f16x8 __attribute__((ext_vector_type(8)));
 
-// two floats -> packed fp16, round to nearest even: gfx950's v_cvt_pk_f16_f32 (bitwise the (_Float16) cast
-// on 2^24 pairs incl. exact ties and subnormal results: tools/micro/cvt_pk_f16_rne.hip)
-__device__ __forceinline__ uint32_t tg_cvt_pk_f16(float a, float b) {
-    uint32_t r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
+// ---- Operand preparation (not the scan): the bank's 16-bit fragment copies, its largest row norm, the
+// queries' fragments.
+
+// A thread's share of the keys' A-operand fragments for the 16x16x32 MFMAs (n_alloc rows x 256 f32 ->
+// 16-bit): thread id = (tile t, chunk c of 32 dims, lane (m, kg)) holds the 8 values
+// K[16 t + pi_row(m)][32 c + 8 kg + 0..7], each float4 passed through cvt.pre and each pair packed by
+// cvt.pk; rows >= n_alloc are 0.  (pi_row: the row order of the float32 tiles, so that the list code
+// sees the same rows.  id by reference: hipcc then knows its range as it does in the kernel itself.)
+template <class Cvt>
+__device__ __forceinline__ u32x4 keyfrag_of(const float* __restrict__ keys, int64_t n_alloc, const int64_t& id,
+                                            const Cvt& cvt) {
+    const int lane = (int)(id & 63), c = (int)((id >> 6) & 7);
+    const int64_t t = id >> 9;
+    const int64_t row = t * 16 + pi_row(lane & 15);
+    u32x4 o = {0u, 0u, 0u, 0u};
+    if (row < n_alloc) {
+        const f32x4* src = reinterpret_cast<const f32x4*>(keys + row * KEY_DIM + 32 * c + 8 * (lane >> 4));
+        const f32x4 a = cvt.pre(src[0]), b = cvt.pre(src[1]);
+        o[0] = cvt.pk(a.x, a.y); o[1] = cvt.pk(a.z, a.w);
+        o[2] = cvt.pk(b.x, b.y); o[3] = cvt.pk(b.z, b.w);
+    }
+    return o;
 }
+struct KeyToBf16 {                 // RNE
+    __device__ __forceinline__ f32x4 pre(f32x4 v) const { return v; }
+    __device__ __forceinline__ uint32_t pk(float x, float y) const { return cvt_pk_bf16(x, y); }
+};
+struct KeyToF16Scaled {            // x scale (a power of two: exact), then RNE
+    float scale;
+    __device__ __forceinline__ f32x4 pre(f32x4 v) const { return v * scale; }
+    __device__ __forceinline__ uint32_t pk(float x, float y) const { return cvt_pk_f16(x, y); }
+};
+
+// the streaming scan's bf16 copy of the keys
+__global__ __launch_bounds__(256) void keyfrag_kernel(const float* __restrict__ keys, int64_t n_alloc,
+                                                      int64_t n_tiles, u32x4* __restrict__ out) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= n_tiles * 8 * 64) return;
+    out[id] = keyfrag_of(keys, n_alloc, id, KeyToBf16{});
+}
+
+// largest squared row norm of the keys (the bits of a non-negative float order like an integer):
+// the error bound of the prefilter scales with it, and the constant-shift softmax of pass 1
+// needs it <= 1.  One wave per row.
+__global__ __launch_bounds__(256) void key_norm_kernel(const float* __restrict__ keys, int64_t n_rows,
+                                                       uint32_t* __restrict__ n2max_bits) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(keys + row * KEY_DIM + 4 * lane);
+    float s = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);
+    if (lane == 0) atomicMax(n2max_bits, __float_as_uint(s));
+}
+
 // the power of two that puts a positive float's value in [2^13, 2^14) (1 for zero / denormal input)
 __device__ __forceinline__ float tg_scale_to_2p13(float mx) {
     const uint32_t E = (__float_as_uint(mx) >> 23) & 0xFFu;
@@ -91,7 +140,7 @@ __device__ __forceinline__ float tg_scale_to_2p13(float mx) {
 // of two that puts its largest element in [2^13, 2^14) (qscale[q]; rows past B: copies of the last query):
 // group grp of 16 queries, chunk c, lane (j, kg): Q[16 grp + j][32 c + 8 kg + 0..7].  One workgroup per group.
 __global__ __launch_bounds__(256) void qfrag_f16_kernel(const float* __restrict__ ehat, int64_t B,
-                                                        ts_u32x4* __restrict__ out, float* __restrict__ qscale) {
+                                                        u32x4* __restrict__ out, float* __restrict__ qscale) {
     __shared__ float sh_mx[16][17];
     const int t = threadIdx.x, j = t & 15, part = t >> 4;            // 16 parts of 16 elements per query
     const int64_t grp = blockIdx.x;
@@ -120,29 +169,19 @@ __global__ __launch_bounds__(256) void qfrag_f16_kernel(const float* __restrict_
         const float sc = sh_mx[jj][16];
         const f32x4* src = reinterpret_cast<const f32x4*>(ehat + qq * KEY_DIM + 32 * c + 8 * kg);
         const f32x4 v0 = src[0] * sc, v1 = src[1] * sc;
-        ts_u32x4 o;
-        o[0] = tg_cvt_pk_f16(v0.x, v0.y); o[1] = tg_cvt_pk_f16(v0.z, v0.w);
-        o[2] = tg_cvt_pk_f16(v1.x, v1.y); o[3] = tg_cvt_pk_f16(v1.z, v1.w);
+        u32x4 o;
+        o[0] = cvt_pk_f16(v0.x, v0.y); o[1] = cvt_pk_f16(v0.z, v0.w);
+        o[2] = cvt_pk_f16(v1.x, v1.y); o[3] = cvt_pk_f16(v1.z, v1.w);
         out[(grp * 8 + c) * 64 + ln] = o;
     }
 }
 
-// keys (n_alloc rows x 256 f32) x scale -> fp16 A-operand fragments, the layout of keyfrag_kernel
+// keys x scale -> fp16: the copy this file's passes read, in the layout of keyfrag_kernel
 __global__ __launch_bounds__(256) void keyfrag_f16_kernel(const float* __restrict__ keys, int64_t n_alloc,
-                                                          int64_t n_tiles, float scale, ts_u32x4* __restrict__ out) {
+                                                          int64_t n_tiles, float scale, u32x4* __restrict__ out) {
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_tiles * 8 * 64) return;
-    const int lane = (int)(id & 63), c = (int)((id >> 6) & 7);
-    const int64_t t = id >> 9;
-    const int64_t row = t * 16 + pi_row(lane & 15);
-    ts_u32x4 o = {0u, 0u, 0u, 0u};
-    if (row < n_alloc) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(keys + row * KEY_DIM + 32 * c + 8 * (lane >> 4));
-        const f32x4 a = src[0] * scale, b = src[1] * scale;
-        o[0] = tg_cvt_pk_f16(a.x, a.y); o[1] = tg_cvt_pk_f16(a.z, a.w);
-        o[2] = tg_cvt_pk_f16(b.x, b.y); o[3] = tg_cvt_pk_f16(b.z, b.w);
-    }
-    out[id] = o;
+    out[id] = keyfrag_of(keys, n_alloc, id, KeyToF16Scaled{scale});
 }
 
 struct TopkGemmArgs {
@@ -214,9 +253,9 @@ __global__ __launch_bounds__(TG_WAVES * 64, 2) void topk_gemm_kernel(TopkGemmArg
     // B operand: lane (n = query j, kg = g) holds Q[j][32 c + 8 g + 0..7] of chunk c as fp16 - converted and
     // scaled once per call by qfrag_f16_kernel (every workgroup of both passes converting its 256 queries
     // itself cost pass A 20 % of its time): 16 bytes per lane and chunk, coalesced
-    ts_u32x4 qf[TG_GQ][8];
+    u32x4 qf[TG_GQ][8];
     {
-        const ts_u32x4* qsrc = reinterpret_cast<const ts_u32x4*>(a.qfrag);
+        const u32x4* qsrc = reinterpret_cast<const u32x4*>(a.qfrag);
         const int64_t n_groups = (a.B + 15) / 16;
 #pragma unroll
         for (int gi = 0; gi < TG_GQ; ++gi) {
@@ -281,9 +320,9 @@ __global__ __launch_bounds__(TG_WAVES * 64, 2) void topk_gemm_kernel(TopkGemmArg
 
     // a tile's 4 x 8 MFMAs (its fragments from LDS or, for the tail tile, straight from memory)
     auto mfma_tile = [&](const char* kt, f32x4 (&acc)[TG_GQ]) __attribute__((always_inline)) {
-        ts_u32x4 kf[8];
+        u32x4 kf[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) kf[c] = *reinterpret_cast<const ts_u32x4*>(kt + c * 1024);
+        for (int c = 0; c < 8; ++c) kf[c] = *reinterpret_cast<const u32x4*>(kt + c * 1024);
 #pragma unroll
         for (int gi = 0; gi < TG_GQ; ++gi) {
             f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
@@ -474,29 +513,6 @@ __global__ __launch_bounds__(256) void topk_gemm_threshold_kernel(const float* _
     }
 }
 
-// topk_exact_dot (topk_stream.h) - the same products in the same order, the same float - with the key
-// row's loads issued in two bursts of 32 instead of sixteen dependent groups of four: a thread that
-// walks a row of its own pays the memory latency twice, not sixteen times
-__device__ __forceinline__ float topk_exact_dot_burst(const float* __restrict__ kr, const float* sh_q) {
-    float acc = 0.f;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        f32x4 kc[32];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) kc[i] = *reinterpret_cast<const f32x4*>(kr + 128 * h + 4 * i);
-#pragma unroll
-        for (int s8 = 0; s8 < 8; ++s8) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg)
-                    acc = __builtin_fmaf(kc[4 * s8 + gg][c], sh_q[128 * h + 16 * s8 + 4 * gg + c], acc);
-            }
-        }
-    }
-    return acc;
-}
-
 // The candidates of one query -> its top k: one workgroup per query.
 //   1. the lists' lengths (n_splits x 4 of them), a prefix sum, the entries compacted into LDS as
 //      64-bit keys (ordered bits of S~, ~row);
@@ -575,7 +591,7 @@ __global__ __launch_bounds__(256, 2) void topk_gemm_rerank_kernel(TopkGemmArgs a
     unsigned long long key = 0ull;
     if (t < nx) {
         const uint32_t row = topk_key_row(kx[t]);
-        key = topk_key(topk_exact_dot_burst(a.keys + (int64_t)row * KEY_DIM, sh_q), row);
+        key = topk_key(topk_exact_dot<8>(a.keys + (int64_t)row * KEY_DIM, sh_q), row);
     }
     __syncthreads();
     kx[t] = key;
@@ -595,7 +611,7 @@ __global__ __launch_bounds__(256, 2) void topk_gemm_rerank_kernel(TopkGemmArgs a
 }
 
 // more candidates than the lists hold (a bank of near-duplicates, or fewer than 16 row groups): every
-// row's float32 similarity (topk_stream.h: topk_brute_force).  A few workgroups walk the queries'
+// row's float32 similarity (topk_merge.h: topk_brute_force).  A few workgroups walk the queries'
 // flags; normally none is set.
 __global__ __launch_bounds__(256) void topk_gemm_brute_kernel(TopkGemmArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[KEY_DIM * 4 + 16 * MAX_TOPK * 8 + MAX_TOPK * 8];

@@ -102,17 +102,20 @@ def test_reference_sh_tables_of_other_degrees(L):
 
 @pytest.mark.parametrize("N,B,k", [(1, 1, 1), (15, 16, 4), (16, 17, 16), (17, 31, 16), (4095, 32, 16), (4097, 33, 7),
                                    (16385, 64, 16), (100_003, 20, 16), (70_000, 160, 16), (1029, 96, 3)])
-def test_stream_topk_ragged_banks(N, B, k):
+def test_stream_topk_ragged_banks(N, B, k, monkeypatch):
     """Persistent stream kernel on banks smaller than the grid, ragged last tiles, more than one
-    supergroup of query groups: indices and values equal to the float64 oracle's."""
+    supergroup of query groups: indices and values equal to the float64 oracle's - and, the two key
+    forms sharing one scan body, the float32-key scan's equal to the default's bit for bit."""
     rng = np.random.default_rng(N + B)
     keys = rng.standard_normal((N, 256)).astype(np.float32)
     keys /= np.linalg.norm(keys, axis=1, keepdims=True)
     qs = rng.standard_normal((B, 256)).astype(np.float32)
     qs /= np.linalg.norm(qs, axis=1, keepdims=True)
-    eng = _native.HipEngine("cuda:0")
-    eng.set_bank(keys, np.zeros((N, 1024), np.float32), np.zeros((N, 3), np.float32), 1000)   # row offset
-    tv, ti = eng.topk_stream(torch.from_numpy(qs).cuda(), k)
+    eng, f32 = _topk_engines(monkeypatch, keys, np.zeros((N, 1024), np.float32), np.zeros((N, 3), np.float32), 1000)   # row offset
+    e = torch.from_numpy(qs).cuda()
+    tv, ti = eng.topk_stream(e, k)
+    fv, fi = f32.topk_stream(e, k)
+    assert torch.equal(ti, fi) and torch.equal(tv, fv)
     s64 = qs.astype(np.float64) @ keys.astype(np.float64).T
     kk = min(k, N)
     rv, ri = O.topk64(s64, kk)
@@ -126,14 +129,14 @@ def test_stream_topk_ragged_banks(N, B, k):
         assert (ti[:, N:] == -1).all()
 
 
-def _topk_engines(monkeypatch, keys, vals, xyz):
+def _topk_engines(monkeypatch, keys, vals, xyz, row_offset=0):
     """(engine with the default bf16-key prefilter, engine streaming the float32 keys)"""
     pre = _native.HipEngine("cuda:0")
     monkeypatch.setenv("RANGE_TOPKS_KEYS", "f32")
     f32 = _native.HipEngine("cuda:0")
     monkeypatch.delenv("RANGE_TOPKS_KEYS")
     for e in (pre, f32):
-        e.set_bank(keys, vals, xyz)
+        e.set_bank(keys, vals, xyz, row_offset)
     return pre, f32
 
 

@@ -14,6 +14,7 @@ import re
 import pytest
 
 from device_asm import device_asm                      # (one compile for all codegen tests)
+from tools import kernel_asm_diff
 from tools.kernel_asm_diff import innermost_mfma_loop as _innermost_mfma_loop
 
 
@@ -61,3 +62,37 @@ def test_inner_loop_of_the_recompute_pass2():
     assert count(r"s_barrier\b") == 2
     moved = [l for l in code if re.match(r"(v_accvgpr_|scratch_)", l)]
     assert not moved, moved[:4]
+
+
+def _listing(cuid):
+    """A listing of two kernels in hipcc's layout, closed by the translation unit's ``__hip_cuid`` object."""
+    def kernel(name, body):
+        return (f"\t.text\n\t.protected\t{name}\n\t.globl\t{name}\n\t.type\t{name},@function\n"
+                f"{name}:\n; %bb.0:\n{body}\ts_endpgm\n"
+                f"\t.section\t.rodata,\"a\",@progbits\n\t.amdhsa_kernel {name}\n\t\t.amdhsa_next_free_vgpr 8\n"
+                f"\t.end_amdhsa_kernel\n\t.text\n.Lfunc_end0:\n\t.size\t{name}, .Lfunc_end0-{name}\n"
+                f"\t.set {name}.num_vgpr, 8\n\t.section\t.AMDGPU.csdata,\"\",@progbits\n; Kernel info:\n"
+                f"; NumVgprs: 8\n; NumAgprs: 0\n; ScratchSize: 0\n; Occupancy: 8\n")
+    return (kernel("first_kernel", "\tv_mov_b32_e32 v0, 0\n") + kernel("last_kernel", "\tv_mov_b32_e32 v1, 1\n") +
+            f"\t.text\n\t.p2alignl 6, 3212836864\n\t.type\t__hip_cuid_{cuid},@object\n\t.section\t.bss,\"aw\",@nobits\n"
+            f"\t.globl\t__hip_cuid_{cuid}\n__hip_cuid_{cuid}:\n\t.byte\t0\n\t.size\t__hip_cuid_{cuid}, 1\n"
+            f"\t.addrsig_sym __hip_cuid_{cuid}\n")
+
+
+def test_asm_diff_ends_a_kernel_at_its_own_end(tmp_path, capsys):
+    """tools/kernel_asm_diff.py: the object hipcc names after a hash of the sources follows the last
+    kernel of a listing and is no part of it - two listings that differ in nothing else hold no
+    differing kernel, and a kernel's chunk still carries its resource block."""
+    a, b = _listing("48af349932bb732f"), _listing("0123456789abcdef")
+    ka, kb = kernel_asm_diff.kernels(a), kernel_asm_diff.kernels(b)
+    assert sorted(ka) == ["first_kernel", "last_kernel"] and ka == kb
+    assert all("; NumAgprs: 0" in k and "; Occupancy: 8" in k and "__hip_cuid" not in k for k in ka.values())
+    (tmp_path / "a.s").write_text(a)
+    (tmp_path / "b.s").write_text(b)
+    assert kernel_asm_diff.main(["kernel_asm_diff", str(tmp_path / "a.s"), str(tmp_path / "b.s")]) == 0
+    out = capsys.readouterr().out
+    assert "differs" not in out and "2 identical" in out
+    # a change inside a kernel is still one
+    (tmp_path / "b.s").write_text(b.replace("v_mov_b32_e32 v1, 1", "v_mov_b32_e32 v1, 2"))
+    kernel_asm_diff.main(["kernel_asm_diff", str(tmp_path / "a.s"), str(tmp_path / "b.s")])
+    assert "differs: last_kernel" in capsys.readouterr().out

@@ -30,10 +30,29 @@ def innermost_mfma_loop(body):
     return best
 
 
+def own_end(name, lines):
+    """Number of lines of a kernel's chunk that are its own: up to its ``.size`` line (its
+    ``.end_amdhsa_kernel`` where there is none) and the resource block that follows it (blank lines,
+    comments, the symbol's ``.set`` lines and their section).  What the assembler puts behind the last
+    kernel - padding, the translation unit's ``__hip_cuid_<hash>`` object - is not the kernel's."""
+    ends = [i for i, l in enumerate(lines) if re.match(rf"\s*\.size\s+{re.escape(name)}\s*,", l)] or \
+           [i for i, l in enumerate(lines) if re.match(r"\s*\.end_amdhsa_kernel\b", l)]
+    n = ends[-1] + 1
+    own = re.compile(rf"\s*($|;|\.set\s+{re.escape(name)}\.|\.section\s+\.AMDGPU\.csdata\b)")
+    while n < len(lines) and own.match(lines[n]):
+        n += 1
+    return n
+
+
 def kernels(text):
-    """{symbol: text from its label to the next global label} for every kernel of a listing."""
+    """{symbol: text from its label to its own end} for every kernel of a listing."""
     chunks = re.split(r"\n(?=[A-Za-z_][\w$.]*:)", text)
-    return {c.split(":", 1)[0]: c for c in chunks if re.search(r"^\s*\.amdhsa_kernel\s", c, re.M)}
+    out = {}
+    for c in chunks:
+        if re.search(r"^\s*\.amdhsa_kernel\s", c, re.M):
+            name, lines = c.split(":", 1)[0], c.split("\n")
+            out[name] = "\n".join(lines[:own_end(name, lines)])
+    return out
 
 
 def instructions(lines):

@@ -39,9 +39,9 @@ __global__ __launch_bounds__(TG_WAVES * 64, OCC) void tg_var(TopkGemmArgs a) {
     const int b1 = (t1 - t0 + stride - 1) / stride;
     const int n_phase = (b1 + TG_KT - 1) / TG_KT;
     const int64_t q0 = (int64_t)qb * TG_QBLOCK + wave * (TG_GQ * 16);
-    ts_u32x4 qf[TG_GQ][8];
+    u32x4 qf[TG_GQ][8];
     {
-        const ts_u32x4* qsrc = reinterpret_cast<const ts_u32x4*>(a.qfrag);
+        const u32x4* qsrc = reinterpret_cast<const u32x4*>(a.qfrag);
         const int64_t n_groups = (a.B + 15) / 16;
 #pragma unroll
         for (int gi = 0; gi < TG_GQ; ++gi) {
@@ -72,11 +72,11 @@ __global__ __launch_bounds__(TG_WAVES * 64, OCC) void tg_var(TopkGemmArgs a) {
     };
     issue(0);
     issue(1);
-    auto read_frags = [&](const char* kt, ts_u32x4 (&kf)[8]) __attribute__((always_inline)) {
+    auto read_frags = [&](const char* kt, u32x4 (&kf)[8]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) kf[c] = *reinterpret_cast<const ts_u32x4*>(kt + c * 1024);
+        for (int c = 0; c < 8; ++c) kf[c] = *reinterpret_cast<const u32x4*>(kt + c * 1024);
     };
-    auto mfmas = [&](ts_u32x4 (&kf)[8], f32x4 (&acc)[TG_GQ]) __attribute__((always_inline)) {
+    auto mfmas = [&](u32x4 (&kf)[8], f32x4 (&acc)[TG_GQ]) __attribute__((always_inline)) {
 #pragma unroll
         for (int gi = 0; gi < TG_GQ; ++gi) {
             f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(TG_WAVES * 64, OCC) void tg_var(TopkGemmArgs a) {
         }
     };
     f32x4 accA[TG_GQ], accB[TG_GQ];
-    ts_u32x4 kf0[8], kf1[8];
+    u32x4 kf0[8], kf1[8];
     bool have_b = false;
     if (NOLDS) {
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
