@@ -209,6 +209,43 @@ int32_t range_posenc_width(int32_t kind, int32_t F);
 int range_posenc_features(range_ctx* ctx, int32_t kind, const double* freq_host, int32_t F,
                           const double* lonlat_dev, int64_t B, double* out_dev, range_stream_t stream);
 
+/* The reference's CSP location encoders (load_model names 'CSP', 'CSP_INat'; range/range.py:141-150,
+ * :251-252; location_models/csp/main/SpatialRelationEncoder.py 'gridcell' / 'theory' features, then the
+ * float32 feed-forward net of module.py:48-229) as one fused launch (csp_kernel.h).
+ * range_set_csp installs a network in the context (replacing an earlier one; the call drains the device):
+ *   kind        : RANGE_POSENC_GRID ('gridcell') or RANGE_POSENC_THEORY ('theory')
+ *   freq_host   : F float64 frequencies, 1 <= F <= 64 (range_amd/csp.py: freq_list)
+ *   n_layers    : linear layers, 1 .. 9 (num_hidden_layer + 1);  widths[i]: output width of layer i, 1 .. 1024
+ *                 (the last is num_filts); layer 0 reads the F * P features
+ *   weights_host[i] : (widths[i], input width) float32 row-major;  biases_host[i] : (widths[i]) float32
+ *   ln_gamma_host[i], ln_beta_host[i] : (widths[i]) float32 for i < n_layers - 1 when use_layn (else unread;
+ *                 the arrays may be NULL without use_layn)
+ *   act         : RANGE_CSP_ACT_*;  skip, use_layn : the reference's skip_connection / use_layn
+ * Every layer computes act(x W^T + b); layers before the last then add x (skip, where input and output
+ * width agree) and apply LayerNorm (biased variance, eps 1e-5 under the root, affine) - in that order.
+ * All host arrays are read during the call.  RANGE_ERR_INVALID: null pointers, anything outside the envelope.
+ * range_csp_width: num_filts of the installed network, 0 without one.  range_csp_tile_rows: locations of
+ * one workgroup's tile (64, or 32 with a width above 512), 0 without a network.
+ * range_csp_encode: lonlat_dev (B,2) float64 (lon,lat) degrees used as they are -> out_dev (B, num_filts)
+ * float32 (4-byte aligned; lonlat_dev 8-byte aligned).  B >= 1, 64-bit indexing; rows are independent of
+ * each other and of B bit for bit; a NaN / infinite coordinate gives a NaN row.
+ * range_csp_encode_grid: the same with at most max_grid workgroups (0: the default cap) - the tiles beyond
+ * are walked grid-stride; same bits.  For tests of that walk. */
+#define RANGE_CSP_ACT_SIGMOID 0
+#define RANGE_CSP_ACT_RELU 1
+#define RANGE_CSP_ACT_LEAKYRELU 2
+#define RANGE_CSP_ACT_TANH 3
+#define RANGE_CSP_ACT_GELU 4
+int range_set_csp(range_ctx* ctx, int32_t kind, const double* freq_host, int32_t F, int32_t n_layers,
+                  const int32_t* widths, const float* const* weights_host, const float* const* biases_host,
+                  const float* const* ln_gamma_host, const float* const* ln_beta_host, int32_t act, int32_t skip,
+                  int32_t use_layn);
+int32_t range_csp_width(const range_ctx* ctx);
+int32_t range_csp_tile_rows(const range_ctx* ctx);
+int range_csp_encode(range_ctx* ctx, const double* lonlat_dev, int64_t B, float* out_dev, range_stream_t stream);
+int range_csp_encode_grid(range_ctx* ctx, const double* lonlat_dev, int64_t B, float* out_dev, int64_t max_grid,
+                          range_stream_t stream);
+
 /* Kernel B, pass 1.  Streaming log-sum-exp statistics of the temperature-scaled logits of
  * range/range.py:213-215 (semantic) and :231-234 (geographic) over THIS ctx's bank rows.
  *   tau_sem, tau_geo : temperatures (range.py:103, 108-109); tau_geo <= 0 disables the geo head

@@ -40,6 +40,7 @@ SYMBOLS = (
     "range_scan_stats_at", "range_p1_splits", "range_check_async_error", "range_stream_read_timed",
     "range_async_error_flag", "range_topk_last", "range_set_temperatures", "range_stats_kept",
     "range_posenc_width", "range_posenc_features",
+    "range_set_csp", "range_csp_width", "range_csp_tile_rows", "range_csp_encode", "range_csp_encode_grid",
 )
 PV_MODES = {"exact": 0, "bf16x3": 1}   # range_set_pv_mode
 
@@ -114,6 +115,13 @@ def load_library() -> C.CDLL:
     lib.range_posenc_width.argtypes = [i32, i32]
     lib.range_posenc_width.restype = i32
     lib.range_posenc_features.argtypes = [vp, i32, vp, i32, vp, i64, vp, vp]
+    lib.range_set_csp.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32]
+    lib.range_csp_width.argtypes = [vp]
+    lib.range_csp_width.restype = i32
+    lib.range_csp_tile_rows.argtypes = [vp]
+    lib.range_csp_tile_rows.restype = i32
+    lib.range_csp_encode.argtypes = [vp, vp, i64, vp, vp]
+    lib.range_csp_encode_grid.argtypes = [vp, vp, i64, vp, i64, vp]
     lib.range_set_pv_mode.argtypes = [vp, i32]
     lib.range_get_pv_mode.argtypes = [vp]
     lib.range_get_pv_mode.restype = i32
@@ -355,6 +363,55 @@ class HipEngine:
                 raise ValueError(f"out has {out.shape[0]} rows for {B} locations")
         _check(self.lib, self.lib.range_posenc_features(self._h, kind, freq.ctypes.data, F, lonlat.data_ptr(), B,
                                                         out.data_ptr(), self._stream()))
+        return out
+
+    def set_csp(self, kind: int, freq: np.ndarray, widths: Sequence[int], weights: Sequence[np.ndarray],
+                biases: Sequence[np.ndarray], ln_gamma: Sequence[Optional[np.ndarray]],
+                ln_beta: Sequence[Optional[np.ndarray]], act: int, skip: bool, use_layn: bool) -> None:
+        """Install a CSP network (range_set_csp; ``range_amd.csp.CspParams`` holds these fields): ``kind``
+        ``posenc.KIND_GRID`` / ``KIND_THEORY``, ``freq`` (F,) float64, per linear layer its output width,
+        (out, in) float32 weight, (out,) bias and - hidden layers with ``use_layn`` - LayerNorm gamma / beta.
+        Replaces an earlier network of this engine."""
+        n = len(widths)
+        if not (len(weights) == len(biases) == len(ln_gamma) == len(ln_beta) == n):
+            raise ValueError("need one weight, bias, gamma and beta entry per layer")
+        freq = np.ascontiguousarray(freq, dtype=np.float64)
+        if freq.ndim != 1:
+            raise ValueError(f"freq must be one-dimensional, got {freq.shape}")
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
+        ws, bs, gs, bes = ([f32(a) for a in arrs] for arrs in (weights, biases, ln_gamma, ln_beta))
+        wd = np.ascontiguousarray(widths, dtype=np.int32)
+        from .posenc import PER_FREQ
+        d_in = PER_FREQ.get(kind, 0) * freq.shape[0]
+        for i in range(n):
+            d_out = int(wd[i])
+            if ws[i].shape != (d_out, d_in) or bs[i].shape != (d_out,):
+                raise ValueError(f"layer {i}: weight {ws[i].shape} / bias {bs[i].shape} do not match ({d_out},{d_in})")
+            if any(a is not None and a.shape != (d_out,) for a in (gs[i], bes[i])):
+                raise ValueError(f"layer {i}: LayerNorm parameters do not match ({d_out},)")
+            d_in = d_out
+        arr = lambda xs: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in xs])   # noqa: E731
+        _check(self.lib, self.lib.range_set_csp(self._h, kind, freq.ctypes.data, freq.shape[0], n, wd.ctypes.data,
+                                                arr(ws), arr(bs), arr(gs), arr(bes), int(act), int(bool(skip)),
+                                                int(bool(use_layn))))
+
+    def csp_encode(self, lonlat: torch.Tensor, out: Optional[torch.Tensor] = None, max_grid: int = 0) -> torch.Tensor:
+        """The installed CSP network (range_csp_encode): ``lonlat`` (B,2) float64 degrees -> (B, num_filts)
+        float32.  ``out``: a contiguous (B, num_filts) float32 view to write into.  ``max_grid``: at most so many
+        workgroups (range_csp_encode_grid; tests of the grid-stride walk)."""
+        self._t(lonlat, torch.float64, (2,))
+        B = lonlat.shape[0]
+        width = self.lib.range_csp_width(self._h)
+        if width <= 0:
+            raise RangeNativeError("no CSP network set on this engine (set_csp)")
+        if out is None:
+            out = self._empty((B, width), torch.float32)
+        else:
+            self._t(out, torch.float32, (width,))
+            if out.shape[0] != B:
+                raise ValueError(f"out has {out.shape[0]} rows for {B} locations")
+        _check(self.lib, self.lib.range_csp_encode_grid(self._h, lonlat.data_ptr(), B, out.data_ptr(), int(max_grid),
+                                                        self._stream()))
         return out
 
     def blend(self, G: torch.Tensor, H: torch.Tensor, beta: float) -> torch.Tensor:

@@ -1,0 +1,122 @@
+"""CSP checkpoint reader for the 'CSP' / 'CSP_INat' models (reference: range/range.py:141-150 ->
+location_models/csp/load_csp.py ``get_csp`` -> csp/main/utils.py ``get_model`` / ``get_spa_encoder`` /
+``get_ffn``).
+
+The reference rebuilds the whole ``LocationImageEncoder`` (class and user heads, the image decoder) and
+calls ``forward(coords, return_feats=True)``; only the feed-forward net behind the spatial encoder
+matters on that path, so only ``params`` and the ``loc_enc.spa_enc.ffn.layers.*`` tensors are read.
+numpy / torch-CPU only: importable, and testable, without a GPU.  The kernel: range_amd/csrc/csp_kernel.h.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+
+from . import posenc
+from .ckpt import _load_file
+
+# range_set_csp(act), include/range_hip.h (csp/main/module.py:33-45)
+ACTIVATIONS = {"sigmoid": 0, "relu": 1, "leakyrelu": 2, "tanh": 3, "gelu": 4}
+#: spa_enc_type -> kernel kind (the feature layouts posenc_kernel.h's arithmetic produces)
+SPA_ENC_KINDS = {"gridcell": posenc.KIND_GRID, "theory": posenc.KIND_THEORY}
+#: what csp/main/utils.py:get_spa_enc_list and get_model know beyond those two
+UNSUPPORTED_SPA_ENC = ("gridcellnorm", "hexagridcell", "theorynorm", "theorydiag", "naive", "rbf", "rff",
+                       "geo_net", "geo_net_fft")
+MAX_FREQ, MAX_WIDTH, MAX_HIDDEN_LAYERS = 64, 1024, 8     # the kernel's envelope (host_plan.h: csp_plan)
+_PREFIX = "loc_enc.spa_enc.ffn.layers."
+
+
+@dataclass
+class CspParams:
+    spa_enc_type: str
+    kind: int                      # posenc.KIND_GRID / KIND_THEORY
+    frequency_num: int
+    min_radius: float
+    max_radius: float
+    freq_init: str
+    freq_list: np.ndarray          # (F,) float64
+    num_hidden_layer: int
+    hidden_dim: int
+    num_filts: int
+    activation: str                # params['spa_f_act']
+    use_layn: bool
+    skip_connection: bool
+    widths: List[int]              # output width of every linear layer; the last is num_filts
+    weights: List[np.ndarray]      # float32 (out, in)
+    biases: List[np.ndarray]       # float32 (out,)
+    ln_gamma: List[Optional[np.ndarray]]   # float32 (out,) for the hidden layers with use_layn, else None
+    ln_beta: List[Optional[np.ndarray]]
+
+    @property
+    def input_dim(self) -> int:
+        return posenc.PER_FREQ[self.kind] * self.frequency_num
+
+
+def cal_freq_list(freq_init: str, frequency_num: int, max_radius, min_radius) -> np.ndarray:
+    """``_cal_freq_list`` (csp/main/SpatialRelationEncoder.py:18-49) in its expression order.  'random' draws
+    from ``np.random`` when the model is BUILT and is not stored in the checkpoint: it cannot be reproduced."""
+    if freq_init == "geometric":
+        if frequency_num < 2:
+            raise ValueError("freq_init='geometric' needs frequency_num >= 2 (the reference divides by frequency_num - 1)")
+        return posenc.cal_freq_list(frequency_num, max_radius, min_radius)
+    if freq_init == "nerf":
+        return np.pi * np.exp2(np.arange(frequency_num).astype(float))
+    raise NotImplementedError(
+        f"freq_init={freq_init!r}: " + ("the reference draws these frequencies at random when it builds the model and "
+                                       "does not store them" if freq_init == "random" else "unknown"))
+
+
+def _np32(t, what: str, shape) -> np.ndarray:
+    a = np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t))
+    if a.shape != tuple(shape):
+        raise ValueError(f"{what}: shape {a.shape}, params say {tuple(shape)}")
+    if a.dtype != np.float32:
+        raise ValueError(f"{what}: dtype {a.dtype}, the reference's network is float32")
+    return a
+
+
+def read_csp_checkpoint(path: str) -> CspParams:
+    """``{'params', 'state_dict'}`` as csp/main/trainer.py saves it -> ``CspParams``.  ``params['device']``,
+    the heads (``class_emb``, ``user_emb``, ``img_dec`` / ``loc_dec``) and the ``spa_enc.*`` aliases of the
+    same tensors are ignored.  NotImplementedError names an unsupported ``spa_enc_type`` / ``freq_init``;
+    ValueError: a tensor whose shape is not what ``params`` say, or a network outside the kernel's envelope."""
+    ck = _load_file(path)
+    params, sd = ck["params"], ck["state_dict"]
+    spa = params["spa_enc_type"]
+    if spa not in SPA_ENC_KINDS:
+        raise NotImplementedError(f"CSP spa_enc_type={spa!r}: only {sorted(SPA_ENC_KINDS)} are implemented")
+    kind = SPA_ENC_KINDS[spa]
+    F = int(params["frequency_num"])
+    act = params["spa_f_act"]
+    if act not in ACTIVATIONS:
+        raise NotImplementedError(f"CSP spa_f_act={act!r} activation not recognized")   # module.py:45
+    freq_init = params["freq_init"]
+    n_hidden, hidden, num_filts = int(params["num_hidden_layer"]), int(params["hidden_dim"]), int(params["num_filts"])
+    if not 1 <= F <= MAX_FREQ:
+        raise ValueError(f"CSP frequency_num={F}: 1 .. {MAX_FREQ} are supported")
+    if n_hidden > MAX_HIDDEN_LAYERS:
+        raise ValueError(f"CSP num_hidden_layer={n_hidden}: at most {MAX_HIDDEN_LAYERS} are supported")
+    freqs = np.ascontiguousarray(cal_freq_list(freq_init, F, params["max_radius"], params["min_radius"]), dtype=np.float64)
+    widths = [hidden] * max(n_hidden, 0) + [num_filts]          # module.py:177-209
+    for w in widths:
+        if not 1 <= w <= MAX_WIDTH:
+            raise ValueError(f"CSP layer width {w}: 1 .. {MAX_WIDTH} are supported")
+    use_layn, skip = bool(params["use_layn"]), bool(params["skip_connection"])
+    ws, bs, gs, bes = [], [], [], []
+    d_in = posenc.PER_FREQ[kind] * F
+    for i, d_out in enumerate(widths):
+        pre = f"{_PREFIX}{i}."
+        ws.append(_np32(sd[pre + "linear.weight"], pre + "linear.weight", (d_out, d_in)))
+        bs.append(_np32(sd[pre + "linear.bias"], pre + "linear.bias", (d_out,)))
+        has_ln = use_layn and i + 1 < len(widths)
+        if has_ln != (pre + "layernorm.weight" in sd):
+            raise ValueError(f"{pre}layernorm.*: {'missing' if has_ln else 'present'} although use_layn={use_layn}")
+        gs.append(_np32(sd[pre + "layernorm.weight"], pre + "layernorm.weight", (d_out,)) if has_ln else None)
+        bes.append(_np32(sd[pre + "layernorm.bias"], pre + "layernorm.bias", (d_out,)) if has_ln else None)
+        d_in = d_out
+    if f"{_PREFIX}{len(widths)}.linear.weight" in sd:
+        raise ValueError("state_dict has more layers than params['num_hidden_layer'] says")
+    return CspParams(spa, kind, F, float(params["min_radius"]), float(params["max_radius"]), freq_init, freqs,
+                     n_hidden, hidden, num_filts, act, use_layn, skip, widths, ws, bs, gs, bes)

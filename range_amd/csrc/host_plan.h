@@ -651,4 +651,108 @@ inline PosencPlan posenc_plan(int kind, int F, int64_t B) {
     return p;
 }
 
+// The CSP location encoders (csp_kernel.h; range_set_csp / range_csp_encode): 'gridcell' or 'theory'
+// features of F frequencies, then n_layers float32 linear layers - every one followed by the activation,
+// the hidden ones (all but the last) also by the skip connection (where input and output width agree)
+// and torch's LayerNorm.  A workgroup of CSP_BLOCK threads takes a tile of 64 locations (32 when a width
+// is beyond 512: the layer's whole output tile lives in the four waves' accumulators, 128 registers a
+// lane) whose activations stay in ONE LDS image of `ld` floats a row; `ld` is odd, so the 32 rows an MFMA
+// A operand reads fall into 32 banks.  Weights are packed per layer in the order the kernel reads them
+// (csp_pack_weights): K padded to CSP_KGROUP, N to CSP_NTILE, with zeros.
+enum { CSP_ACT_SIGMOID = 0, CSP_ACT_RELU = 1, CSP_ACT_LEAKYRELU = 2, CSP_ACT_TANH = 3, CSP_ACT_GELU = 4, CSP_ACTS = 5 };
+constexpr int CSP_BLOCK = 256;
+constexpr int CSP_MAX_F = 64, CSP_MAX_WIDTH = 1024, CSP_MAX_LAYERS = 9;   // <= 8 hidden layers and the output layer
+constexpr int CSP_KGROUP = 8;             // k of one 16-byte weight fragment: four 32x32x2 steps
+constexpr int CSP_NTILE = 32;             // output columns of one MFMA tile
+constexpr int CSP_ACC_TILES = 8;          // 32x32 accumulator tiles of a wave: m_tiles * (n tiles of the wave)
+constexpr int64_t CSP_MAX_GRID = 2048;    // workgroups of a launch (one fits a CU); more tiles are walked grid-stride
+
+struct CspLayerPlan {
+    int in = 0, out = 0;                 // true widths
+    int k_groups = 0, n_tiles = 0;       // ceil(in / CSP_KGROUP), ceil(out / CSP_NTILE)
+    bool skip = false, layn = false;
+    size_t w_off = 0, b_off = 0, g_off = 0, be_off = 0;   // floats into the packed parameters (g/be: layn only)
+    int k_pad() const { return k_groups * CSP_KGROUP; }
+    int n_pad() const { return n_tiles * CSP_NTILE; }
+};
+
+struct CspPlan {
+    bool valid = false;
+    const char* why = "";                // what is outside the envelope
+    int in0 = 0, out_width = 0, n_layers = 0;
+    CspLayerPlan layer[CSP_MAX_LAYERS];
+    int tile_rows = 0, m_tiles = 0, ld = 0;
+    size_t lds_bytes = 0, packed_floats = 0;
+    int64_t n_tiles = 0;
+    unsigned grid = 0;
+    int block = CSP_BLOCK;
+    int64_t tiles_of(int64_t blk) const { return blk < n_tiles ? (n_tiles - blk + grid - 1) / grid : 0; }
+};
+
+// kind: PE_GRID or PE_THEORY.  widths[i]: output width of layer i (n_layers >= 1; the last is num_filts).
+// max_grid: a smaller cap on the grid than CSP_MAX_GRID (0: none) - for tests of the grid-stride walk.
+inline CspPlan csp_plan(int kind, int F, int n_layers, const int* widths, bool skip, bool use_layn, int64_t B,
+                        int64_t max_grid = 0) {
+    CspPlan p;
+    if (kind != PE_GRID && kind != PE_THEORY) { p.why = "spa_enc kind (gridcell or theory)"; return p; }
+    if (F < 1 || F > CSP_MAX_F) { p.why = "frequency_num outside 1 .. 64"; return p; }
+    if (n_layers < 1 || n_layers > CSP_MAX_LAYERS || !widths) { p.why = "more than 8 hidden layers"; return p; }
+    if (B < 1 || B > (INT64_C(1) << 48) || max_grid < 0) { p.why = "batch size"; return p; }
+    p.in0 = posenc_per_freq(kind) * F;
+    p.n_layers = n_layers;
+    int widest = p.in0, in = p.in0;
+    size_t off = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        const int out = widths[i];
+        if (out < 1 || out > CSP_MAX_WIDTH) { p.why = "layer width outside 1 .. 1024"; return p; }
+        CspLayerPlan& l = p.layer[i];
+        l.in = in;
+        l.out = out;
+        l.k_groups = (in + CSP_KGROUP - 1) / CSP_KGROUP;
+        l.n_tiles = (out + CSP_NTILE - 1) / CSP_NTILE;
+        const bool hidden = i + 1 < n_layers;
+        l.skip = hidden && skip && in == out;
+        l.layn = hidden && use_layn;
+        l.w_off = off;
+        off += (size_t)l.k_pad() * l.n_pad();
+        l.b_off = off;
+        off += l.n_pad();
+        if (l.layn) { l.g_off = off; l.be_off = off + l.n_pad(); off += 2 * (size_t)l.n_pad(); }
+        widest = std::max(widest, out);
+        in = out;
+    }
+    p.out_width = in;
+    p.packed_floats = off;
+    p.m_tiles = widest <= 512 ? 2 : 1;
+    p.tile_rows = 32 * p.m_tiles;
+    // a row holds any layer's input padded to CSP_KGROUP and any output padded to CSP_NTILE; odd
+    p.ld = (widest + CSP_NTILE - 1) / CSP_NTILE * CSP_NTILE + 1;
+    p.lds_bytes = (size_t)p.tile_rows * p.ld * sizeof(float);
+    p.n_tiles = (B + p.tile_rows - 1) / p.tile_rows;
+    p.grid = (unsigned)std::min(p.n_tiles, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID);
+    p.valid = true;
+    return p;
+}
+
+// where W[n][k] of a layer goes in its packed weights: (n tile, k group, lane, step) with lane = 32 * (k & 1)
+// + n % 32 and step = (k % 8) / 2 - lane `l` of a wave reads the four floats of its k group at once and feeds
+// step s of them to the MFMA as B[k = l >> 5][n = l & 31]
+inline size_t csp_packed_index(const CspLayerPlan& l, int n, int k) {
+    const int nt = n / CSP_NTILE, kg = k / CSP_KGROUP, kk = k % CSP_KGROUP;
+    const int lane = 32 * (kk & 1) + n % CSP_NTILE;
+    return (((size_t)nt * l.k_groups + kg) * 64 + lane) * 4 + kk / 2;
+}
+
+// one layer's parameters into `dst` (p.packed_floats floats, zeroed by the caller): weight (out, in) row-major,
+// bias (out), and gamma / beta (out) where the layer has a LayerNorm
+inline void csp_pack_layer(const CspPlan& p, int i, const float* weight, const float* bias, const float* gamma,
+                           const float* beta, float* dst) {
+    const CspLayerPlan& l = p.layer[i];
+    for (int n = 0; n < l.out; ++n) {
+        for (int k = 0; k < l.in; ++k) dst[l.w_off + csp_packed_index(l, n, k)] = weight[(size_t)n * l.in + k];
+        dst[l.b_off + n] = bias[n];
+        if (l.layn) { dst[l.g_off + n] = gamma[n]; dst[l.be_off + n] = beta[n]; }
+    }
+}
+
 }  // namespace range_host

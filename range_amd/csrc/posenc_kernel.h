@@ -50,6 +50,25 @@ __device__ __forceinline__ double posenc_dot2_unfused(double x, double ux, doubl
     return p + q;
 }
 
+// The sines and cosines of ONE (location, frequency) - what this kernel and the CSP encoders' feature
+// phase (csp_kernel.h) both evaluate.  Theory: (sin, cos) of the three angles, v[0..5].
+__device__ __forceinline__ void posenc_theory_item(double x, double y, double f, double* v) {
+    constexpr double S3H = 1.7320508075688772 / 2.0;   // math.sqrt(3) / 2.0
+    const double a1 = posenc_dot2_unfused(x, 1.0, y, 0.0);
+    const double a2 = posenc_dot2_unfused(x, -0.5, y, S3H);
+    const double a3 = posenc_dot2_unfused(x, -0.5, y, -S3H);
+    sincos(a1 * f, &v[0], &v[1]);
+    sincos(a2 * f, &v[2], &v[3]);
+    sincos(a3 * f, &v[4], &v[5]);
+}
+
+// grid and the sphere kinds: (sin, cos) of lon * f and of lat * f
+__device__ __forceinline__ void posenc_lonlat_item(double x, double y, double f, double& sal, double& cal, double& sat,
+                                                   double& cat) {
+    sincos(x * f, &sal, &cal);
+    sincos(y * f, &sat, &cat);
+}
+
 struct PosencArgs {
     const double* freq;     // (F) float64, device
     const double* lonlat;   // (B,2) float64, (lon,lat) degrees
@@ -98,17 +117,10 @@ __global__ __launch_bounds__(POSENC_BLOCK) void posenc_features_kernel(PosencArg
             const double x = a.lonlat[2 * b], y = a.lonlat[2 * b + 1];
             const double f = a.freq[i];
             if constexpr (KIND == PE_THEORY) {
-                constexpr double S3H = 1.7320508075688772 / 2.0;   // math.sqrt(3) / 2.0
-                const double a1 = posenc_dot2_unfused(x, 1.0, y, 0.0);
-                const double a2 = posenc_dot2_unfused(x, -0.5, y, S3H);
-                const double a3 = posenc_dot2_unfused(x, -0.5, y, -S3H);
-                sincos(a1 * f, &v[0], &v[1]);
-                sincos(a2 * f, &v[2], &v[3]);
-                sincos(a3 * f, &v[4], &v[5]);
+                posenc_theory_item(x, y, f, v);
             } else {
                 double sal, cal, sat, cat;
-                sincos(x * f, &sal, &cal);
-                sincos(y * f, &sat, &cat);
+                posenc_lonlat_item(x, y, f, sal, cal, sat, cat);
                 if constexpr (KIND == PE_GRID) {
                     v[0] = sal; v[1] = cal; v[2] = sat; v[3] = cat;
                 } else if constexpr (KIND == PE_SPHEREC) {

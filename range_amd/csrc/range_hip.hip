@@ -28,6 +28,7 @@
 #include "attend_small.h"
 #include "encoder_kernel.h"
 #include "posenc_kernel.h"
+#include "csp_kernel.h"
 
 using namespace range_hip;
 using namespace range_host;
@@ -138,6 +139,17 @@ struct range_ctx {
         struct Table { std::vector<double> host; DevBuf<double> dev; };
         std::vector<std::unique_ptr<Table>> tables;
     } posenc;
+    // range_set_csp: the installed CSP network - its plan (for B = 1), the packed parameters, the frequencies
+    struct Csp {
+        bool has = false;
+        int kind = 0, F = 0, act = 0;
+        bool skip = false, layn = false;
+        int widths[CSP_MAX_LAYERS] = {};
+        CspPlan plan;
+        DevBuf<float> d_params;
+        DevBuf<double> d_freq;
+        DevBuf<CspLayerArgs> d_layers;
+    } csp;
     // words of host memory the kernels can write (hipHostMallocMapped; async_err.h): set by a persistent
     // kernel whose bounded wait for other workgroups gave up; read - without synchronising - by the
     // next call and behind every synchronising exit (check_async_error)
@@ -1708,3 +1720,98 @@ static void (*kept_stats_kernel_for(int n_pairs, bool geo))(KeptStatsArgs) {
         {kept_stats_kernel<7, true>, kept_stats_kernel<7, false>}, {kept_stats_kernel<8, true>, kept_stats_kernel<8, false>}};
     return kept_kernels[n_pairs - 1][!geo];
 }
+
+// ---- the CSP location encoders (csp_kernel.h), by tile height (32 m_tiles rows) and activation
+static void (*csp_kernel_for(int m_tiles, int act))(CspArgs) {
+    static void (*const csp_kernels[2][CSP_ACTS])(CspArgs) = {
+        {csp_encode_kernel<1, 0>, csp_encode_kernel<1, 1>, csp_encode_kernel<1, 2>, csp_encode_kernel<1, 3>, csp_encode_kernel<1, 4>},
+        {csp_encode_kernel<2, 0>, csp_encode_kernel<2, 1>, csp_encode_kernel<2, 2>, csp_encode_kernel<2, 3>, csp_encode_kernel<2, 4>}};
+    return csp_kernels[m_tiles - 1][act];
+}
+
+extern "C" {
+
+int range_set_csp(range_ctx* c, int32_t kind, const double* freq_host, int32_t F, int32_t n_layers, const int32_t* widths,
+                  const float* const* weights, const float* const* biases, const float* const* ln_gamma,
+                  const float* const* ln_beta, int32_t act, int32_t skip, int32_t use_layn) {
+    if (!c || !freq_host || !widths || !weights || !biases) return fail(RANGE_ERR_INVALID, "null argument");
+    if (act < 0 || act >= CSP_ACTS) return fail(RANGE_ERR_INVALID, "activation %d", act);
+    if (n_layers < 1 || n_layers > CSP_MAX_LAYERS)
+        return fail(RANGE_ERR_INVALID, "%d linear layers (1 .. %d: at most 8 hidden layers)", n_layers, CSP_MAX_LAYERS);
+    int w[CSP_MAX_LAYERS];
+    for (int i = 0; i < n_layers; ++i) w[i] = widths[i];
+    const CspPlan p = csp_plan(kind, F, n_layers, w, skip != 0, use_layn != 0, 1);
+    if (!p.valid) return fail(RANGE_ERR_INVALID, "CSP network outside the supported envelope: %s", p.why);
+    for (int i = 0; i < n_layers; ++i) {
+        if (!weights[i] || !biases[i]) return fail(RANGE_ERR_INVALID, "null parameters of layer %d", i);
+        if (p.layer[i].layn && (!ln_gamma || !ln_beta || !ln_gamma[i] || !ln_beta[i]))
+            return fail(RANGE_ERR_INVALID, "null LayerNorm parameters of layer %d", i);
+    }
+    std::vector<float> packed(p.packed_floats, 0.0f);
+    for (int i = 0; i < n_layers; ++i)
+        csp_pack_layer(p, i, weights[i], biases[i], p.layer[i].layn ? ln_gamma[i] : nullptr,
+                       p.layer[i].layn ? ln_beta[i] : nullptr, packed.data());
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    // a launch in flight on any stream may still read the parameters this call replaces
+    HIP_TRY(hipDeviceSynchronize());
+    c->csp.has = false;
+    HIP_TRY(c->csp.d_params.upload(packed));
+    HIP_TRY(c->csp.d_freq.upload(std::vector<double>(freq_host, freq_host + F)));
+    std::vector<CspLayerArgs> layers;
+    for (int i = 0; i < n_layers; ++i) {
+        const CspLayerPlan& l = p.layer[i];
+        layers.push_back(CspLayerArgs{l.out, l.n_tiles, l.k_groups, l.skip, l.layn, (uint32_t)l.w_off, (uint32_t)l.b_off,
+                                      (uint32_t)l.g_off, (uint32_t)l.be_off});
+    }
+    HIP_TRY(c->csp.d_layers.upload(layers));
+    c->csp.kind = kind;
+    c->csp.F = F;
+    c->csp.act = act;
+    c->csp.skip = skip != 0;
+    c->csp.layn = use_layn != 0;
+    std::copy(w, w + n_layers, c->csp.widths);
+    c->csp.plan = p;
+    c->csp.has = true;
+    return RANGE_OK;
+}
+
+int32_t range_csp_width(const range_ctx* c) { return c && c->csp.has ? c->csp.plan.out_width : 0; }
+
+int32_t range_csp_tile_rows(const range_ctx* c) { return c && c->csp.has ? c->csp.plan.tile_rows : 0; }
+
+int range_csp_encode_grid(range_ctx* c, const double* lonlat, int64_t B, float* out, int64_t max_grid,
+                          range_stream_t stream) {
+    if (!c || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
+    if (!c->csp.has) return fail(RANGE_ERR_INVALID, "no CSP network set (range_set_csp)");
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (max_grid < 0) return fail(RANGE_ERR_INVALID, "max_grid must be >= 0");
+    if (reinterpret_cast<uintptr_t>(lonlat) % 8 || reinterpret_cast<uintptr_t>(out) % 4)
+        return fail(RANGE_ERR_INVALID, "lonlat_dev must be 8-byte aligned, out_dev 4-byte aligned");
+    const range_ctx::Csp& m = c->csp;
+    const CspPlan p = csp_plan(m.kind, m.F, m.plan.n_layers, m.widths, m.skip, m.layn, B, max_grid);
+    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld locations: %s", (long long)B, p.why);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    CspArgs a{};
+    a.freq = m.d_freq.p;
+    a.lonlat = lonlat;
+    a.params = m.d_params.p;
+    a.out = out;
+    a.B = B;
+    a.n_tiles = p.n_tiles;
+    a.F = m.F;
+    a.kind = m.kind;
+    a.layer = m.d_layers.p;
+    a.n_layers = p.n_layers;
+    a.ld = p.ld;
+    a.in0 = p.in0;
+    a.in0_pad = p.layer[0].k_pad();
+    return launch(csp_kernel_for(p.m_tiles, m.act), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
+}
+
+int range_csp_encode(range_ctx* c, const double* lonlat, int64_t B, float* out, range_stream_t stream) {
+    return range_csp_encode_grid(c, lonlat, B, out, 0, stream);
+}
+
+}  // extern "C"

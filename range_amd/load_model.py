@@ -12,9 +12,11 @@ def load_model(model_name="RANGE+", pretrained_path=None, device="cuda", temp=No
 
     Args:
         model_name: 'RANGE', 'RANGE+', 'SatCLIP' (the encoder alone, range.py:117-122) or one of
-            the training-free encoders 'Direct', 'Cartesian_3D', 'Wrap' (range.py:152-173).
-        pretrained_path: SatCLIP checkpoint (e.g. satclip-vit16-l40.ckpt); the reference demands
-            it for every model name, also those that never read it.
+            the training-free encoders 'Direct', 'Cartesian_3D', 'Wrap' (range.py:152-173), 'Theory',
+            's2vec_*', or 'CSP' / 'CSP_INat' (range.py:140-150: a CSP checkpoint, range_amd/csp.py).
+        pretrained_path: SatCLIP checkpoint (e.g. satclip-vit16-l40.ckpt), or the CSP checkpoint
+            (model_*.pth.tar) for 'CSP' / 'CSP_INat'; the reference demands it for every model name,
+            also those that never read it.
         device: 'cuda' / 'cuda:N'.
         temp, geo_temp: the softmax temperatures of the semantic / the geographic (RANGE+ only) retrieval
             instead of the reference's 15 (RANGE), 12 and 40 (RANGE+) - finite, > 0, at most 1000.  They

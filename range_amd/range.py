@@ -23,6 +23,7 @@ from ._hostpool import POOL
 from .bank import PreparedBank
 from .bankfile import load_any as load_bank
 from .ckpt import EncoderParams, read_checkpoint
+from .csp import ACTIVATIONS as CSP_ACTIVATIONS, CspParams, read_csp_checkpoint
 
 TEMP_RANGE = 15.0        # range/range.py:103
 TEMP_RANGE_PLUS = 12.0   # range/range.py:108
@@ -315,6 +316,78 @@ class PosencLocationModel(nn.Module):
         return self._engine[0].posenc_features(x, self._kind, self.freq_list).to(dtype)
 
 
+# the reference's banners (range.py:142; :148 prints a garbled 'Using CSP-IN75.97lkjhat')
+_CSP_MODELS = {"CSP": "Using CSP-FMOW", "CSP_INat": "Using CSP-INat"}
+
+
+class _CspLayer(nn.Module):
+    """One ``SingleFeedForwardNN`` (csp/main/module.py:48-132): ``linear`` and, where the checkpoint has one,
+    ``layernorm`` - float32, frozen."""
+
+    def __init__(self, p: CspParams, i: int, device):
+        super().__init__()
+        frozen = lambda a: nn.Parameter(torch.as_tensor(a, dtype=torch.float32, device=device), requires_grad=False)  # noqa: E731
+        d_out, d_in = p.weights[i].shape
+        self.linear = nn.Linear(d_in, d_out, device="meta")
+        self.linear.weight, self.linear.bias = frozen(p.weights[i]), frozen(p.biases[i])
+        if p.ln_gamma[i] is not None:
+            self.layernorm = nn.LayerNorm(d_out, device="meta")
+            self.layernorm.weight, self.layernorm.bias = frozen(p.ln_gamma[i]), frozen(p.ln_beta[i])
+
+
+class _CspFfn(nn.Module):
+    def __init__(self, p: CspParams, device):
+        super().__init__()
+        self.layers = nn.ModuleList([_CspLayer(p, i, device) for i in range(len(p.widths))])
+
+
+class _CspSpaEnc(nn.Module):
+    def __init__(self, p: CspParams, device):
+        super().__init__()
+        self.ffn = _CspFfn(p, device)
+        self.frequency_num, self.min_radius, self.max_radius = p.frequency_num, p.min_radius, p.max_radius
+        self.freq_init, self.freq_list = p.freq_init, p.freq_list
+        self.spa_embed_dim, self.input_embed_dim = p.num_filts, p.input_dim
+
+
+class _CspLocEnc(nn.Module):
+    def __init__(self, p: CspParams, device):
+        super().__init__()
+        self.spa_enc = _CspSpaEnc(p, device)
+        self.num_filts = p.num_filts
+
+
+class CspLocationModel(nn.Module):
+    """``model.loc_model`` of 'CSP' / 'CSP_INat' (range.py:143, 149: ``get_csp(path)``, a
+    ``LocationImageEncoder``): a module whose call maps (B,2) (lon, lat) degrees - used as they are - to the
+    (B, num_filts) float32 location embedding on the engine's GPU (``forward(coords, return_feats=True)``
+    there), and whose parameters are the feed-forward net's, frozen, float32, on that GPU, under the
+    reference's names (``loc_enc.spa_enc.ffn.layers.{i}.linear.weight`` ...).  As for SatCLIP they are a
+    read-only MIRROR: the arithmetic runs in the engine (csp_kernel.h) on its own packed copy.  The class and
+    user heads and the image decoder of the checkpoint are not loaded: this path never evaluates them."""
+
+    def __init__(self, engine, p: CspParams):
+        super().__init__()
+        self.loc_enc = _CspLocEnc(p, engine.device)
+        self.loc_emb_dim = p.num_filts
+        self._engine = [engine]
+        engine.set_csp(p.kind, p.freq_list, p.widths, p.weights, p.biases, p.ln_gamma, p.ln_beta,
+                       CSP_ACTIVATIONS[p.activation], p.skip_connection, p.use_layn)
+        self.eval()
+
+    @torch.no_grad()
+    def forward(self, coords, return_feats: bool = True):
+        if not return_feats:
+            raise NotImplementedError("CSP: only return_feats=True (the location embedding) is implemented")
+        return self.encode(_as_coords(coords, self._engine[0].device))
+
+    def encode(self, x: torch.Tensor) -> torch.Tensor:
+        """``x``: (B,2) float64 on the engine's GPU -> (B, num_filts) float32."""
+        if x.shape[0] == 0:
+            return torch.empty((0, self.loc_emb_dim), dtype=torch.float32, device=x.device)
+        return self._engine[0].csp_encode(x)
+
+
 class _EncoderBase(nn.Module):
     """What the one-GPU and the row-sharded encoder share: ``args``, ``engine``, ``loc_model``."""
 
@@ -419,10 +492,20 @@ class LocationEncoder(_EncoderBase):
             self.engine = _native.HipEngine(self._device)
             self.loc_model = PosencLocationModel(self.engine, self.location_model_name)
             self._posenc = spec
+        elif self.location_model_name in _CSP_MODELS:                   # range.py:140-150
+            print(_CSP_MODELS[self.location_model_name])
+            csp = read_csp_checkpoint(args.pretrained_path)
+            self.location_feature_dim = csp.num_filts                   # (256 for the published checkpoints: :144, :150)
+            self._model_id = None
+            self.csp_params = csp
+            self._device = _device_of(args.device)
+            self.engine = _native.HipEngine(self._device)
+            self.loc_model = CspLocationModel(self.engine, csp)
+            self._csp = True
         else:
-            # the reference dispatches more encoder families here (GeoCLIP, TaxaBind, CSP, SINR;
-            # range.py:124-150, 190-197): third-party pretrained baselines that need their own
-            # packages and checkpoints, out of scope for this engine
+            # the reference dispatches more encoder families here (GeoCLIP, TaxaBind, SINR;
+            # range.py:124-138, 190-197): third-party pretrained baselines that need their own
+            # packages (geoclip, rshf) and download their weights, out of scope for this engine
             raise NotImplementedError(f"{self.location_model_name} not implemented")
         self._freeze()
 
@@ -445,6 +528,9 @@ class LocationEncoder(_EncoderBase):
         if getattr(self, "_posenc", None) is not None:
             # Theory / s2vec_*: a device tensor of the coordinates' dtype (range.py:269-275)
             return self.loc_model.encode(x, self.loc_model.result_dtype(coords))
+        if getattr(self, "_csp", False):
+            # CSP / CSP_INat: a float32 device tensor whatever the coordinates' dtype (range.py:251-252)
+            return self.loc_model.encode(x)
         if getattr(self, "_coord_mode", None) is not None:
             # Direct / Wrap return a device tensor, Cartesian_3D a host ndarray (its rad_to_cart
             # runs in numpy, range.py:265-268)

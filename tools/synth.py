@@ -254,3 +254,63 @@ def write_ylm_source(path: str, L: int) -> str:
     with open(path, "w") as f:
         f.write("\n".join(lines))
     return path
+
+
+# ---- CSP checkpoints (csp/main/trainer.py saves {'params', 'state_dict'}; load_csp.py:10-31 reads them) ----
+def make_csp_checkpoint(spa_enc_type: str = "gridcell", F: int = 32, hidden: int = 512, layers: int = 1,
+                        act: str = "gelu", use_layn: bool = True, skip: bool = True, num_filts: int = 256,
+                        min_radius: float = 0.001, max_radius: float = 360.0, seed: int = 77,
+                        freq_init: str = "geometric", num_classes: int = 5, cnn_feat_dim: int = 8,
+                        device: str = "cuda:3") -> Dict[str, object]:
+    """A checkpoint dict with the reference's key names: ``params`` as ``get_csp`` / ``get_model`` /
+    ``get_ffn`` read them and the ``state_dict`` of a ``LocationImageEncoder`` - the feed-forward net under
+    ``loc_enc.spa_enc.ffn.layers.{i}.linear.*`` / ``.layernorm.*`` (float32, numpy-seeded: Xavier-uniform
+    weights, non-zero biases, LayerNorm gamma / beta away from 1 / 0), the same tensors under the ``spa_enc.*``
+    alias, and the heads a reader of the location embedding must ignore (``class_emb``, ``user_emb``, ``img_dec``,
+    each under its aliases).  ``layers``: num_hidden_layer (0: one layer from the features to num_filts).
+    ``device``: ``params['device']``, the training job's - the reference moves the model there (load_csp.py:21),
+    range_amd ignores it."""
+    import torch
+
+    rng = np.random.default_rng(seed)
+    d_in = {"gridcell": 4, "gridcellnorm": 4, "theory": 6, "theorynorm": 6, "theorydiag": 6}.get(spa_enc_type, 4) * F
+    widths = [hidden] * max(layers, 0) + [num_filts]
+    sd: Dict[str, object] = {}
+
+    def put(name, arr):
+        t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+        sd[f"loc_enc.spa_enc.ffn.layers.{name}"] = t
+        sd[f"spa_enc.ffn.layers.{name}"] = t          # LocationImageEncoder.spa_enc is loc_enc.spa_enc (models.py:187)
+
+    for i, d_out in enumerate(widths):
+        a = math.sqrt(6.0 / (d_in + d_out))
+        put(f"{i}.linear.weight", rng.uniform(-a, a, size=(d_out, d_in)))
+        put(f"{i}.linear.bias", rng.uniform(-0.3, 0.3, size=(d_out,)))
+        if use_layn and i + 1 < len(widths):
+            put(f"{i}.layernorm.weight", rng.uniform(0.5, 1.5, size=(d_out,)))
+            put(f"{i}.layernorm.bias", rng.uniform(-0.5, 0.5, size=(d_out,)))
+        d_in = d_out
+    f32 = lambda *shape: torch.from_numpy(rng.standard_normal(shape).astype(np.float32))   # noqa: E731
+    class_emb, user_emb = f32(num_classes, num_filts), f32(1, num_filts)
+    for pre in ("loc_enc.", ""):
+        sd[pre + "class_emb.weight"] = class_emb
+        sd[pre + "user_emb.weight"] = user_emb
+    sd["img_dec.weight"], sd["img_dec.bias"] = f32(num_filts, cnn_feat_dim), f32(num_filts)
+    params = {
+        "spa_enc_type": spa_enc_type, "num_loc_feats": 2, "num_classes": num_classes, "num_filts": num_filts,
+        "num_users": 1, "device": device, "train_loss": "full_loss", "unsuper_loss": "contsoftmax",
+        "cnn_feat_dim": cnn_feat_dim, "map_range": (-180, 180, -90, 90), "frequency_num": F,
+        "max_radius": max_radius, "min_radius": min_radius, "spa_f_act": act, "freq_init": freq_init,
+        "num_rbf_anchor_pts": 200, "rbf_kernal_size": 1.0, "spa_enc_use_postmat": True,
+        "num_hidden_layer": layers, "dropout": 0.5, "hidden_dim": hidden, "use_layn": use_layn,
+        "skip_connection": skip, "dataset": "fmow", "lr": 0.001,
+    }
+    return {"params": params, "state_dict": sd}
+
+
+def write_csp_checkpoint(path: str, **kw) -> str:
+    import torch
+
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(make_csp_checkpoint(**kw), path)
+    return path
