@@ -246,6 +246,27 @@ int range_csp_encode(range_ctx* ctx, const double* lonlat_dev, int64_t B, float*
 int range_csp_encode_grid(range_ctx* ctx, const double* lonlat_dev, int64_t B, float* out_dev, int64_t max_grid,
                           range_stream_t stream);
 
+/* The checkerboard task's nearest support point (the reference's evaluation/checkerboarddataset.py:78-107:
+ * assign_closest_label; :175-194: the nearest-neighbour statistic) as one scan (checker_kernel.h).  For every
+ * query i the support j with the smallest haversine term
+ *     a = sin(dlat/2)^2 + cos(lat1[i]) cos(lat2[j]) sin(dlon/2)^2,   dlon = lon2[j] - lon1[i], dlat likewise,
+ * in float64, the reference's expression order, nothing contracted; equal a: the lower j (numpy.argmin); a NaN
+ * a never wins.
+ *   q_lonlat_rad_dev : (Q,2) float64 (lon, lat) RADIANS (the host converts with numpy.radians);
+ *   s_lonlat_rad_dev : (S,2) likewise;  exclude_self : skip the pair j == i (needs Q == S >= 2)
+ *   max_chunks       : 0: the launch plan splits the support over so many workgroups per query block that a
+ *                      small Q still fills the chip; n > 0: at most n.  The result does not depend on it.
+ *   idx_dev          : (Q) int64, -1 for a query without a valid pair
+ *   dist_dev         : (Q) float64 or null: 2 atan2(sqrt(a), sqrt(1 - a)) of the winner - the reference's
+ *                      distance at radius 1 - NaN where idx is -1
+ * All device pointers 8-byte aligned; Q, S <= 2^40, 64-bit indexing.  A split scan keeps chunks * Q * 16
+ * bytes of partial results in the context's workspace: calls on one context are to be ordered by the caller.
+ * RANGE_ERR_INVALID: a null ctx / q / s / idx pointer, Q or S < 1, exclude_self with Q != S or S < 2, a
+ * negative max_chunks. */
+int range_nearest_support(range_ctx* ctx, const double* q_lonlat_rad_dev, int64_t Q, const double* s_lonlat_rad_dev,
+                          int64_t S, int32_t exclude_self, int32_t max_chunks, int64_t* idx_dev, double* dist_dev,
+                          range_stream_t stream);
+
 /* Kernel B, pass 1.  Streaming log-sum-exp statistics of the temperature-scaled logits of
  * range/range.py:213-215 (semantic) and :231-234 (geographic) over THIS ctx's bank rows.
  *   tau_sem, tau_geo : temperatures (range.py:103, 108-109); tau_geo <= 0 disables the geo head

@@ -1,6 +1,7 @@
 """range_amd - MI355X-native engine for the RANGE / RANGE+ retrieval-augmented geo-embedding
 forward path of mvrl/RANGE (``load_model(...)(locs)``), its batch driver (``save_embeddings``) and
-the downstream ridge probe (``evaluate_npz``).  See DESIGN.md."""
+the downstream ridge probe (``evaluate_npz``), with the dataset factory (``get_dataset``) for the generated
+checkerboard tasks (``CheckerDataset``) in front.  See DESIGN.md."""
 from .load_model import load_model  # noqa: F401
 from .range import LocationEncoder  # noqa: F401
 
@@ -13,7 +14,13 @@ def __getattr__(name):
     if name == "evaluate_npz":
         from .evaluate import evaluate_npz
         return evaluate_npz
+    if name == "get_dataset":
+        from .load_dataset import get_dataset
+        return get_dataset
+    if name == "CheckerDataset":
+        from .checker import CheckerDataset
+        return CheckerDataset
     raise AttributeError(f"module 'range_amd' has no attribute {name!r}")
 
 
-__all__ = ["load_model", "LocationEncoder", "save_embeddings", "evaluate_npz"]
+__all__ = ["load_model", "LocationEncoder", "save_embeddings", "evaluate_npz", "get_dataset", "CheckerDataset"]

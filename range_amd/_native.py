@@ -41,6 +41,7 @@ SYMBOLS = (
     "range_async_error_flag", "range_topk_last", "range_set_temperatures", "range_stats_kept",
     "range_posenc_width", "range_posenc_features",
     "range_set_csp", "range_csp_width", "range_csp_tile_rows", "range_csp_encode", "range_csp_encode_grid",
+    "range_nearest_support",
 )
 PV_MODES = {"exact": 0, "bf16x3": 1}   # range_set_pv_mode
 
@@ -122,6 +123,7 @@ def load_library() -> C.CDLL:
     lib.range_csp_tile_rows.restype = i32
     lib.range_csp_encode.argtypes = [vp, vp, i64, vp, vp]
     lib.range_csp_encode_grid.argtypes = [vp, vp, i64, vp, i64, vp]
+    lib.range_nearest_support.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     lib.range_set_pv_mode.argtypes = [vp, i32]
     lib.range_get_pv_mode.argtypes = [vp]
     lib.range_get_pv_mode.restype = i32
@@ -413,6 +415,22 @@ class HipEngine:
         _check(self.lib, self.lib.range_csp_encode_grid(self._h, lonlat.data_ptr(), B, out.data_ptr(), int(max_grid),
                                                         self._stream()))
         return out
+
+    def nearest_support(self, q_rad: torch.Tensor, s_rad: torch.Tensor, exclude_self: bool = False, max_chunks: int = 0,
+                        want_dist: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """The checkerboard task's nearest support point (range_nearest_support): ``q_rad`` (Q,2) and ``s_rad``
+        (S,2) float64 (lon, lat) RADIANS -> (``idx`` (Q,) int64, ``dist`` (Q,) float64 great-circle distance at
+        radius 1, or None without ``want_dist``).  ``exclude_self``: skip the pair j == i (Q == S).  ``max_chunks``:
+        at most so many workgroups share a query block's support (0: the plan's choice); same result."""
+        self._t(q_rad, torch.float64, (2,))
+        self._t(s_rad, torch.float64, (2,))
+        Q, S = q_rad.shape[0], s_rad.shape[0]
+        idx = self._empty((Q,), torch.int64)
+        dist = self._empty((Q,), torch.float64) if want_dist else None
+        _check(self.lib, self.lib.range_nearest_support(self._h, q_rad.data_ptr(), Q, s_rad.data_ptr(), S,
+                                                        int(bool(exclude_self)), int(max_chunks), idx.data_ptr(),
+                                                        _ptr(dist), self._stream()))
+        return idx, dist
 
     def blend(self, G: torch.Tensor, H: torch.Tensor, beta: float) -> torch.Tensor:
         """(1-beta)*G + beta*H with the reference's float32 rounding (range.py:238)."""

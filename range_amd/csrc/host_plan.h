@@ -755,4 +755,53 @@ inline void csp_pack_layer(const CspPlan& p, int i, const float* weight, const f
     }
 }
 
+// The nearest-support scan of the checkerboard task (checker_kernel.h; range_nearest_support): one thread per
+// query, workgroups of CHECKER_BLOCK queries (grid x, walked grid-stride), support tiles of CHECKER_TILE points
+// in LDS (lon, lat, cos lat: 3 doubles a point), the tiles dealt round-robin to `chunks` workgroups per query
+// block (grid y).  Q alone fills the chip only from CHECKER_TARGET_WG query blocks on (2048 = 256 CUs x 8
+// workgroups of 4 waves, the CU's 32 waves): below that the support is split so that query blocks x chunks
+// reaches it, every chunk keeping at least one tile, at most CHECKER_MAX_CHUNKS.  With more than one chunk
+// the partial (a, index) pairs take chunks * Q * 16 bytes of workspace and a merge launch follows.
+constexpr int CHECKER_BLOCK = 256;
+constexpr int CHECKER_TILE = 256;
+constexpr int CHECKER_MAX_CHUNKS = 64;
+constexpr int64_t CHECKER_TARGET_WG = 2048;
+constexpr int64_t CHECKER_MAX_GRID = 1 << 20;      // query blocks of a launch; more are walked grid-stride
+constexpr int64_t CHECKER_MAX_POINTS = INT64_C(1) << 40;
+
+struct CheckerPlan {
+    bool valid = false;
+    int tile = CHECKER_TILE, block = CHECKER_BLOCK;
+    int64_t q_blocks = 0, s_tiles = 0;
+    unsigned grid_x = 0;                // workgroups over the query blocks
+    int chunks = 0;                     // grid y
+    unsigned merge_grid = 0;            // chunks > 1: workgroups of the merge launch
+    size_t lds_bytes = 0;
+    size_t ws_pairs = 0, ws_bytes = 0;  // chunks > 1: chunks * Q partial pairs, a double and an int64 each
+    // query blocks workgroup x walks (x, x + grid_x, ...); tiles chunk y walks (y, y + chunks, ...)
+    int64_t blocks_of(int64_t x) const { return x < q_blocks ? (q_blocks - x + grid_x - 1) / grid_x : 0; }
+    int64_t tiles_of(int64_t y) const { return y < s_tiles ? (s_tiles - y + chunks - 1) / chunks : 0; }
+};
+
+// max_chunks: 0 the plan's choice, n > 0 at most n chunks (tests of the split; never more than the tiles).
+// Invalid: Q or S < 1 or beyond 2^40, exclude_self with Q != S or S < 2, a negative max_chunks.
+inline CheckerPlan checker_plan(int64_t Q, int64_t S, bool exclude_self, int max_chunks) {
+    CheckerPlan p;
+    if (Q < 1 || S < 1 || Q > CHECKER_MAX_POINTS || S > CHECKER_MAX_POINTS || max_chunks < 0) return p;
+    if (exclude_self && (Q != S || S < 2)) return p;
+    p.q_blocks = (Q + CHECKER_BLOCK - 1) / CHECKER_BLOCK;
+    p.s_tiles = (S + CHECKER_TILE - 1) / CHECKER_TILE;
+    p.grid_x = (unsigned)std::min(p.q_blocks, CHECKER_MAX_GRID);
+    const int64_t want = max_chunks > 0 ? (int64_t)max_chunks : (CHECKER_TARGET_WG + p.q_blocks - 1) / p.q_blocks;
+    p.chunks = (int)std::min(std::min(want, p.s_tiles), (int64_t)CHECKER_MAX_CHUNKS);
+    p.lds_bytes = (size_t)3 * CHECKER_TILE * sizeof(double);
+    if (p.chunks > 1) {
+        p.ws_pairs = (size_t)p.chunks * (size_t)Q;
+        p.ws_bytes = p.ws_pairs * 16;
+        p.merge_grid = (unsigned)std::min(p.q_blocks, CHECKER_MAX_GRID);
+    }
+    p.valid = true;
+    return p;
+}
+
 }  // namespace range_host

@@ -29,6 +29,7 @@
 #include "encoder_kernel.h"
 #include "posenc_kernel.h"
 #include "csp_kernel.h"
+#include "checker_kernel.h"
 
 using namespace range_hip;
 using namespace range_host;
@@ -150,6 +151,11 @@ struct range_ctx {
         DevBuf<double> d_freq;
         DevBuf<CspLayerArgs> d_layers;
     } csp;
+    // range_nearest_support: the chunks' partial (a, index) pairs of a split scan (checker_kernel.h)
+    struct Checker {
+        DevBuf<double> ws_a;
+        DevBuf<int64_t> ws_idx;
+    } checker;
     // words of host memory the kernels can write (hipHostMallocMapped; async_err.h): set by a persistent
     // kernel whose bounded wait for other workgroups gave up; read - without synchronising - by the
     // next call and behind every synchronising exit (check_async_error)
@@ -1812,6 +1818,49 @@ int range_csp_encode_grid(range_ctx* c, const double* lonlat, int64_t B, float* 
 
 int range_csp_encode(range_ctx* c, const double* lonlat, int64_t B, float* out, range_stream_t stream) {
     return range_csp_encode_grid(c, lonlat, B, out, 0, stream);
+}
+
+}  // extern "C"
+
+// ---- the checkerboard task's nearest-support scan (checker_kernel.h)
+extern "C" {
+
+int range_nearest_support(range_ctx* c, const double* q, int64_t Q, const double* sup, int64_t S, int32_t exclude_self,
+                          int32_t max_chunks, int64_t* idx, double* dist, range_stream_t stream) {
+    if (!c || !q || !sup || !idx) return fail(RANGE_ERR_INVALID, "null argument");
+    if (Q < 1 || S < 1) return fail(RANGE_ERR_INVALID, "Q and S must be > 0");
+    if (max_chunks < 0) return fail(RANGE_ERR_INVALID, "max_chunks must be >= 0");
+    if (exclude_self && (Q != S || S < 2))
+        return fail(RANGE_ERR_INVALID, "exclude_self needs the same Q = S >= 2 points on both sides (Q = %lld, S = %lld)",
+                    (long long)Q, (long long)S);
+    if (reinterpret_cast<uintptr_t>(q) % 8 || reinterpret_cast<uintptr_t>(sup) % 8 || reinterpret_cast<uintptr_t>(idx) % 8 ||
+        reinterpret_cast<uintptr_t>(dist) % 8)
+        return fail(RANGE_ERR_INVALID, "the device pointers must be 8-byte aligned");
+    const CheckerPlan p = checker_plan(Q, S, exclude_self != 0, max_chunks);
+    if (!p.valid) return fail(RANGE_ERR_INVALID, "Q = %lld, S = %lld: too many points", (long long)Q, (long long)S);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    const hipStream_t s = (hipStream_t)stream;
+    CheckerArgs a{};
+    a.q = q;
+    a.s = sup;
+    a.Q = Q;
+    a.S = S;
+    a.q_blocks = p.q_blocks;
+    a.s_tiles = p.s_tiles;
+    a.exclude_self = exclude_self != 0;
+    a.idx = idx;
+    a.dist = dist;
+    if (p.chunks > 1) {
+        if (c->checker.ws_a.ensure(p.ws_pairs) != hipSuccess || c->checker.ws_idx.ensure(p.ws_pairs) != hipSuccess)
+            return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of partial results)", p.ws_bytes);
+        a.part_a = c->checker.ws_a.p;
+        a.part_idx = c->checker.ws_idx.p;
+    }
+    if (int rc = launch(checker_scan_kernel, dim3(p.grid_x, (unsigned)p.chunks), dim3(p.block), p.lds_bytes, s, a)) return rc;
+    if (p.chunks == 1) return RANGE_OK;
+    return launch(checker_merge_kernel, dim3(p.merge_grid), dim3(p.block), 0, s, (const double*)a.part_a,
+                  (const int64_t*)a.part_idx, (int32_t)p.chunks, Q, idx, dist);
 }
 
 }  // extern "C"
