@@ -246,6 +246,42 @@ int range_csp_encode(range_ctx* ctx, const double* lonlat_dev, int64_t B, float*
 int range_csp_encode_grid(range_ctx* ctx, const double* lonlat_dev, int64_t B, float* out_dev, int64_t max_grid,
                           range_stream_t stream);
 
+/* The class head of those models (csp/main/models.py:135-173: class_emb, a bias-free Linear(num_filts, C), then
+ * a sigmoid - the "geo prior") as a launch of its own behind the encoder (csp_head_kernel.h).
+ * range_set_csp_head installs class_emb_host, (C, num_filts) float32 row-major, 1 <= C <= 32768, behind the
+ * installed network (RANGE_ERR_INVALID without one: its num_filts is the head's); it replaces an earlier head
+ * and drains the device.  range_set_csp drops the head.  range_csp_classes: C, 0 without a head.
+ * range_csp_head_cols_per_pass: columns one workgroup finishes per pass (the plan's; 0 without a head).
+ * range_csp_head: feats_dev (B, num_filts) float32 -> out_dev
+ *   RANGE_CSP_HEAD_PROBS  : sigmoid(feats W^T), (B, M) float32
+ *   RANGE_CSP_HEAD_LOGITS : feats W^T, (B, M) float32      (eval_single_class)
+ *   RANGE_CSP_HEAD_SUM    : the sum over all C classes of the sigmoid, (B) float32 (float32 additions in a
+ *                           fixed order; class_ids_dev must be NULL, M = C)
+ * class_ids_dev: NULL - all classes, M must be C - or M int32 class ids on the device (any order, repeats
+ * allowed, M <= 2^24): column j of out is class class_ids_dev[j].  Every output is one k-ordered float32 fma
+ * chain: its bits do not depend on B, the grid, the stream or the other columns of the call - a subset call
+ * returns the full call's columns bit for bit.  A NaN row of feats gives a NaN row.  Ids on the device are the
+ * caller's contract (an id outside [0, C) reads class 0 / C - 1: memory-safe, the column meaningless);
+ * range_csp_check_ids validates M ids in HOST memory against the installed head (RANGE_ERR_INVALID names the
+ * first bad one).  All indexing of out is 64-bit; the pointers are 4-byte aligned.
+ * range_csp_head_grid: at most max_grid workgroups (0: the default cap); same bits.  For tests.
+ * range_csp_predict: lonlat_dev (B,2) float64 -> range_csp_encode into a workspace of the context, then
+ * range_csp_head, on `stream`, in chunks of at most 65536 locations (<= 64 MiB of workspace): the same bits as
+ * the two calls.  One range_csp_predict per context at a time (the workspace is the context's). */
+#define RANGE_CSP_HEAD_PROBS 0
+#define RANGE_CSP_HEAD_LOGITS 1
+#define RANGE_CSP_HEAD_SUM 2
+int range_set_csp_head(range_ctx* ctx, const float* class_emb_host, int32_t C);
+int32_t range_csp_classes(const range_ctx* ctx);
+int32_t range_csp_head_cols_per_pass(const range_ctx* ctx);
+int range_csp_check_ids(range_ctx* ctx, const int32_t* class_ids_host, int32_t M);
+int range_csp_head(range_ctx* ctx, const float* feats_dev, int64_t B, const int32_t* class_ids_dev, int32_t M,
+                   int32_t mode, float* out_dev, range_stream_t stream);
+int range_csp_head_grid(range_ctx* ctx, const float* feats_dev, int64_t B, const int32_t* class_ids_dev, int32_t M,
+                        int32_t mode, float* out_dev, int64_t max_grid, range_stream_t stream);
+int range_csp_predict(range_ctx* ctx, const double* lonlat_dev, int64_t B, const int32_t* class_ids_dev, int32_t M,
+                      int32_t mode, float* out_dev, range_stream_t stream);
+
 /* The checkerboard task's nearest support point (the reference's evaluation/checkerboarddataset.py:78-107:
  * assign_closest_label; :175-194: the nearest-neighbour statistic) as one scan (checker_kernel.h).  For every
  * query i the support j with the smallest haversine term

@@ -25,6 +25,7 @@ MAX_TOPK = 16
 PROF_ENCODER, PROF_SCAN_STATS, PROF_ATTEND, PROF_TOPK_STREAM, PROF_TOPK_MERGE, PROF_KEPT_STATS = 0, 1, 2, 3, 4, 5
 COORD_DIRECT, COORD_CARTESIAN3D, COORD_WRAP = 0, 1, 2   # range_coord_features(mode)
 COORD_DIMS = {COORD_DIRECT: 2, COORD_CARTESIAN3D: 3, COORD_WRAP: 4}
+CSP_HEAD_PROBS, CSP_HEAD_LOGITS, CSP_HEAD_SUM = 0, 1, 2   # range_csp_head(mode)
 
 # every symbol include/range_hip.h declares
 SYMBOLS = (
@@ -41,6 +42,8 @@ SYMBOLS = (
     "range_async_error_flag", "range_topk_last", "range_set_temperatures", "range_stats_kept",
     "range_posenc_width", "range_posenc_features",
     "range_set_csp", "range_csp_width", "range_csp_tile_rows", "range_csp_encode", "range_csp_encode_grid",
+    "range_set_csp_head", "range_csp_classes", "range_csp_head_cols_per_pass", "range_csp_check_ids", "range_csp_head",
+    "range_csp_head_grid", "range_csp_predict",
     "range_nearest_support",
 )
 PV_MODES = {"exact": 0, "bf16x3": 1}   # range_set_pv_mode
@@ -123,6 +126,15 @@ def load_library() -> C.CDLL:
     lib.range_csp_tile_rows.restype = i32
     lib.range_csp_encode.argtypes = [vp, vp, i64, vp, vp]
     lib.range_csp_encode_grid.argtypes = [vp, vp, i64, vp, i64, vp]
+    lib.range_set_csp_head.argtypes = [vp, vp, i32]
+    lib.range_csp_classes.argtypes = [vp]
+    lib.range_csp_classes.restype = i32
+    lib.range_csp_head_cols_per_pass.argtypes = [vp]
+    lib.range_csp_head_cols_per_pass.restype = i32
+    lib.range_csp_check_ids.argtypes = [vp, vp, i32]
+    lib.range_csp_head.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp]
+    lib.range_csp_head_grid.argtypes = [vp, vp, i64, vp, i32, i32, vp, i64, vp]
+    lib.range_csp_predict.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp]
     lib.range_nearest_support.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     lib.range_set_pv_mode.argtypes = [vp, i32]
     lib.range_get_pv_mode.argtypes = [vp]
@@ -414,6 +426,69 @@ class HipEngine:
                 raise ValueError(f"out has {out.shape[0]} rows for {B} locations")
         _check(self.lib, self.lib.range_csp_encode_grid(self._h, lonlat.data_ptr(), B, out.data_ptr(), int(max_grid),
                                                         self._stream()))
+        return out
+
+    def set_csp_head(self, class_emb: np.ndarray) -> None:
+        """Install the class head behind the installed CSP network (range_set_csp_head): ``class_emb``
+        (num_classes, num_filts) float32, the reference's bias-free ``class_emb.weight``.  ``set_csp`` drops it."""
+        w = np.ascontiguousarray(class_emb, dtype=np.float32)
+        width = self.lib.range_csp_width(self._h)
+        if w.ndim != 2 or (width > 0 and w.shape[1] != width):
+            raise ValueError(f"class_emb {w.shape} does not match (num_classes, {width})")
+        _check(self.lib, self.lib.range_set_csp_head(self._h, w.ctypes.data, w.shape[0]))
+
+    @property
+    def csp_classes(self) -> int:
+        return int(self.lib.range_csp_classes(self._h))
+
+    def csp_class_ids(self, ids) -> torch.Tensor:
+        """Class ids for ``csp_head`` / ``csp_predict`` as a contiguous (M,) int32 tensor on the engine's GPU.  Ids
+        that come from the host - a sequence, an ndarray, a CPU tensor - are validated against the installed head
+        (range_csp_check_ids); a tensor already on the GPU is the caller's contract."""
+        if torch.is_tensor(ids) and ids.is_cuda:
+            if ids.device != self.device or ids.ndim != 1 or ids.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"class ids: a 1-D int32 / int64 tensor on {self.device}, got {ids.dtype} {tuple(ids.shape)} on {ids.device}")
+            return ids.to(torch.int32).contiguous()
+        a = ids.numpy() if torch.is_tensor(ids) else np.asarray(ids)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or a.size < 1:
+            raise ValueError(f"class ids: a non-empty 1-D integer sequence, got {a.dtype} {a.shape}")
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("class ids beyond int32")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        _check(self.lib, self.lib.range_csp_check_ids(self._h, a.ctypes.data, a.shape[0]))
+        return torch.from_numpy(a).to(self.device)
+
+    def _csp_head_out(self, B: int, ids, mode: int):
+        C_ = self.csp_classes
+        if C_ <= 0:
+            raise RangeNativeError("no CSP class head set on this engine (set_csp_head)")
+        if mode == CSP_HEAD_SUM and ids is not None:
+            raise ValueError("SUM runs over all classes: no class ids")
+        dev_ids = None if ids is None else self.csp_class_ids(ids)
+        M = C_ if dev_ids is None else dev_ids.shape[0]
+        out = self._empty((B,) if mode == CSP_HEAD_SUM else (B, M), torch.float32)
+        return dev_ids, M, out
+
+    def csp_head(self, feats: torch.Tensor, ids=None, mode: int = CSP_HEAD_PROBS, max_grid: int = 0) -> torch.Tensor:
+        """The class head on embeddings (range_csp_head): ``feats`` (B, num_filts) float32 -> (B, M) float32
+        probabilities (``CSP_HEAD_PROBS``) or logits (``CSP_HEAD_LOGITS``), M the number of ``ids`` (None: all
+        classes), or (B,) sums of all classes' probabilities (``CSP_HEAD_SUM``)."""
+        self._t(feats, torch.float32, (self.lib.range_csp_width(self._h),))
+        B = feats.shape[0]
+        dev_ids, M, out = self._csp_head_out(B, ids, mode)
+        if B:
+            _check(self.lib, self.lib.range_csp_head_grid(self._h, feats.data_ptr(), B, _ptr(dev_ids), M, int(mode),
+                                                          out.data_ptr(), int(max_grid), self._stream()))
+        return out
+
+    def csp_predict(self, lonlat: torch.Tensor, ids=None, mode: int = CSP_HEAD_PROBS) -> torch.Tensor:
+        """Encoder and class head in one call (range_csp_predict): ``lonlat`` (B,2) float64 degrees -> as ``csp_head``."""
+        self._t(lonlat, torch.float64, (2,))
+        B = lonlat.shape[0]
+        dev_ids, M, out = self._csp_head_out(B, ids, mode)
+        if B:
+            _check(self.lib, self.lib.range_csp_predict(self._h, lonlat.data_ptr(), B, _ptr(dev_ids), M, int(mode),
+                                                        out.data_ptr(), self._stream()))
         return out
 
     def nearest_support(self, q_rad: torch.Tensor, s_rad: torch.Tensor, exclude_self: bool = False, max_chunks: int = 0,

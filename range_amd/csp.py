@@ -25,7 +25,9 @@ SPA_ENC_KINDS = {"gridcell": posenc.KIND_GRID, "theory": posenc.KIND_THEORY}
 UNSUPPORTED_SPA_ENC = ("gridcellnorm", "hexagridcell", "theorynorm", "theorydiag", "naive", "rbf", "rff",
                        "geo_net", "geo_net_fft")
 MAX_FREQ, MAX_WIDTH, MAX_HIDDEN_LAYERS = 64, 1024, 8     # the kernel's envelope (host_plan.h: csp_plan)
+MAX_CLASSES = 32768                                      # ... of the class head (host_plan.h: csp_head_plan)
 _PREFIX = "loc_enc.spa_enc.ffn.layers."
+_CLASS_EMB = "loc_enc.class_emb"
 
 
 @dataclass
@@ -48,6 +50,8 @@ class CspParams:
     biases: List[np.ndarray]       # float32 (out,)
     ln_gamma: List[Optional[np.ndarray]]   # float32 (out,) for the hidden layers with use_layn, else None
     ln_beta: List[Optional[np.ndarray]]
+    num_classes: int = 0                     # read_csp_checkpoint(class_head=True): params['num_classes']
+    class_emb: Optional[np.ndarray] = None   # ... and float32 (num_classes, num_filts), bias-free
 
     @property
     def input_dim(self) -> int:
@@ -77,11 +81,14 @@ def _np32(t, what: str, shape) -> np.ndarray:
     return a
 
 
-def read_csp_checkpoint(path: str) -> CspParams:
+def read_csp_checkpoint(path: str, class_head: bool = False) -> CspParams:
     """``{'params', 'state_dict'}`` as csp/main/trainer.py saves it -> ``CspParams``.  ``params['device']``,
     the heads (``class_emb``, ``user_emb``, ``img_dec`` / ``loc_dec``) and the ``spa_enc.*`` aliases of the
     same tensors are ignored.  NotImplementedError names an unsupported ``spa_enc_type`` / ``freq_init``;
-    ValueError: a tensor whose shape is not what ``params`` say, or a network outside the kernel's envelope."""
+    ValueError: a tensor whose shape is not what ``params`` say, or a network outside the kernel's envelope.
+    ``class_head=True`` also reads the class head (models.py:187-190: ``class_emb``, a bias-free
+    ``Linear(num_filts, num_classes)``) from ``loc_enc.class_emb.weight`` into ``class_emb`` / ``num_classes``;
+    ValueError: the key missing, a ``class_emb.bias`` present, ``num_classes`` outside 1 .. 32768."""
     ck = _load_file(path)
     params, sd = ck["params"], ck["state_dict"]
     spa = params["spa_enc_type"]
@@ -118,5 +125,16 @@ def read_csp_checkpoint(path: str) -> CspParams:
         d_in = d_out
     if f"{_PREFIX}{len(widths)}.linear.weight" in sd:
         raise ValueError("state_dict has more layers than params['num_hidden_layer'] says")
-    return CspParams(spa, kind, F, float(params["min_radius"]), float(params["max_radius"]), freq_init, freqs,
-                     n_hidden, hidden, num_filts, act, use_layn, skip, widths, ws, bs, gs, bes)
+    p = CspParams(spa, kind, F, float(params["min_radius"]), float(params["max_radius"]), freq_init, freqs,
+                  n_hidden, hidden, num_filts, act, use_layn, skip, widths, ws, bs, gs, bes)
+    if class_head:
+        C = int(params["num_classes"])
+        if not 1 <= C <= MAX_CLASSES:
+            raise ValueError(f"CSP num_classes={C}: 1 .. {MAX_CLASSES} are supported")
+        if _CLASS_EMB + ".weight" not in sd:
+            raise ValueError(f"{_CLASS_EMB}.weight: missing from the state_dict (class_head=True)")
+        if _CLASS_EMB + ".bias" in sd:
+            raise ValueError(f"{_CLASS_EMB}.bias: present although the reference's class head has no bias")
+        p.num_classes = C
+        p.class_emb = _np32(sd[_CLASS_EMB + ".weight"], _CLASS_EMB + ".weight", (C, num_filts))
+    return p

@@ -755,6 +755,99 @@ inline void csp_pack_layer(const CspPlan& p, int i, const float* weight, const f
     }
 }
 
+// The CSP class head (csp_head_kernel.h; range_set_csp_head / range_csp_head): sigmoid(X W^T) of (B, num_filts)
+// embeddings and the (num_classes, num_filts) class_emb, bias-free - all classes, or the M classes an id array
+// names.  A workgroup of CSP_BLOCK threads holds a tile of 64 rows of X (32 when num_filts > 512: the LDS rule
+// of the layers) in LDS, row stride `ld` odd, and finishes `cols_per_pass` columns of it per pass: every wave
+// CSP_HEAD_ACC_TILES / m_tiles column tiles, dealt round-robin.  (Half the layers' CSP_ACC_TILES: 64 accumulator
+// registers leave room for two workgroups a CU, so that one's loads, sigmoids and stores run under the other's
+// MFMAs - the head has no second layer to keep a tile resident for.)  A work item is a row tile with
+// `chunks_per_item` consecutive chunks of columns (the X tile is loaded once per item): all chunks for SUM, else
+// the largest of 8, 4, 2, 1 that still leaves CSP_MAX_GRID items.  item = row tile * groups + group.  Items are
+// walked grid-stride under the grid cap.  class_emb is packed like a layer's weight (csp_packed_index).
+enum { CSP_HEAD_PROBS = 0, CSP_HEAD_LOGITS = 1, CSP_HEAD_SUM = 2, CSP_HEAD_MODES = 3 };
+constexpr int CSP_HEAD_ACC_TILES = 4;                 // 32x32 accumulator tiles of a wave
+constexpr int CSP_MAX_CLASSES = 32768;
+constexpr int CSP_HEAD_MAX_M = 1 << 24;               // ids of one call (an id may repeat)
+constexpr int64_t CSP_HEAD_MAX_B = INT64_C(1) << 40;
+
+struct CspHeadPlan {
+    bool valid = false;
+    const char* why = "";
+    int num_filts = 0, num_classes = 0, M = 0, mode = 0;
+    int tile_rows = 0, m_tiles = 0, ld = 0;
+    int k_groups = 0, n_tiles = 0;       // of the packed class_emb: ceil(num_filts / 8), ceil(num_classes / 32)
+    int wave_tiles = 0;                  // column tiles a wave holds: CSP_HEAD_ACC_TILES / m_tiles
+    int cols_per_pass = 0;               // 4 waves * wave_tiles * 32
+    int col_tiles = 0, n_chunks = 0;     // ceil(M / 32), ceil(M / cols_per_pass)
+    int chunks_per_item = 0, groups = 0; // groups = ceil(n_chunks / chunks_per_item) items a row tile
+    int64_t row_tiles = 0, n_items = 0;
+    size_t lds_bytes = 0, packed_floats = 0;
+    unsigned grid = 0;
+    int block = CSP_BLOCK;
+    // the packed class_emb as a layer of csp_packed_index
+    CspLayerPlan layer() const {
+        CspLayerPlan l;
+        l.in = num_filts; l.out = num_classes; l.k_groups = k_groups; l.n_tiles = n_tiles;
+        return l;
+    }
+    int64_t items_of(int64_t blk) const { return blk < n_items ? (n_items - blk + grid - 1) / grid : 0; }
+    // item -> its row tile and its chunks [chunk0, chunk1)
+    void item(int64_t it, int64_t& row_tile, int& chunk0, int& chunk1) const {
+        row_tile = it / groups;
+        chunk0 = (int)(it - row_tile * groups) * chunks_per_item;
+        chunk1 = std::min(chunk0 + chunks_per_item, n_chunks);
+    }
+    // the column tiles wave `w` (0 .. 3) computes in chunk `ch`: the first, and how many (stride 4)
+    int wave_first_tile(int ch, int w) const { return ch * 4 * wave_tiles + w; }
+    int wave_n_tiles(int ch, int w) const {
+        const int t0 = wave_first_tile(ch, w);
+        return col_tiles > t0 ? std::min(wave_tiles, (col_tiles - t0 + 3) / 4) : 0;
+    }
+};
+
+// M: columns of the call (num_classes without an id array).  max_grid: a smaller cap than CSP_MAX_GRID (0: none).
+inline CspHeadPlan csp_head_plan(int num_filts, int num_classes, int64_t M, int64_t B, int mode, int64_t max_grid = 0) {
+    CspHeadPlan p;
+    if (num_filts < 1 || num_filts > CSP_MAX_WIDTH) { p.why = "num_filts outside 1 .. 1024"; return p; }
+    if (num_classes < 1 || num_classes > CSP_MAX_CLASSES) { p.why = "num_classes outside 1 .. 32768"; return p; }
+    if (mode < 0 || mode >= CSP_HEAD_MODES) { p.why = "mode (PROBS, LOGITS or SUM)"; return p; }
+    if (M < 1 || M > CSP_HEAD_MAX_M) { p.why = "M outside 1 .. 2^24"; return p; }
+    if (mode == CSP_HEAD_SUM && M != num_classes) { p.why = "SUM runs over all classes"; return p; }
+    if (B < 1 || B > CSP_HEAD_MAX_B || max_grid < 0) { p.why = "batch size"; return p; }
+    p.num_filts = num_filts; p.num_classes = num_classes; p.M = (int)M; p.mode = mode;
+    p.m_tiles = num_filts <= 512 ? 2 : 1;
+    p.tile_rows = 32 * p.m_tiles;
+    p.k_groups = (num_filts + CSP_KGROUP - 1) / CSP_KGROUP;
+    p.n_tiles = (num_classes + CSP_NTILE - 1) / CSP_NTILE;
+    p.ld = p.k_groups * CSP_KGROUP + 1;                  // odd
+    p.wave_tiles = CSP_HEAD_ACC_TILES / p.m_tiles;
+    p.cols_per_pass = 4 * p.wave_tiles * CSP_NTILE;
+    p.col_tiles = (p.M + CSP_NTILE - 1) / CSP_NTILE;
+    p.n_chunks = (p.M + p.cols_per_pass - 1) / p.cols_per_pass;
+    p.row_tiles = (B + p.tile_rows - 1) / p.tile_rows;
+    p.chunks_per_item = 1;
+    if (mode == CSP_HEAD_SUM) p.chunks_per_item = p.n_chunks;
+    else
+        for (int g = 8; g > 1; g /= 2)
+            if (p.row_tiles * ((p.n_chunks + g - 1) / g) >= CSP_MAX_GRID) { p.chunks_per_item = g; break; }
+    p.groups = (p.n_chunks + p.chunks_per_item - 1) / p.chunks_per_item;
+    p.n_items = p.row_tiles * p.groups;
+    // X tile, and (SUM) the four waves' partial row sums
+    p.lds_bytes = ((size_t)p.tile_rows * p.ld + (size_t)4 * p.tile_rows) * sizeof(float);
+    p.packed_floats = (size_t)p.n_tiles * CSP_NTILE * p.k_groups * CSP_KGROUP;
+    p.grid = (unsigned)std::min(p.n_items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID);
+    p.valid = true;
+    return p;
+}
+
+// class_emb (num_classes, num_filts) row-major into `dst` (p.packed_floats floats, zeroed by the caller)
+inline void csp_pack_head(const CspHeadPlan& p, const float* class_emb, float* dst) {
+    const CspLayerPlan l = p.layer();
+    for (int n = 0; n < p.num_classes; ++n)
+        for (int k = 0; k < p.num_filts; ++k) dst[csp_packed_index(l, n, k)] = class_emb[(size_t)n * p.num_filts + k];
+}
+
 // The nearest-support scan of the checkerboard task (checker_kernel.h; range_nearest_support): one thread per
 // query, workgroups of CHECKER_BLOCK queries (grid x, walked grid-stride), support tiles of CHECKER_TILE points
 // in LDS (lon, lat, cos lat: 3 doubles a point), the tiles dealt round-robin to `chunks` workgroups per query

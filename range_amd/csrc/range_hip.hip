@@ -29,6 +29,7 @@
 #include "encoder_kernel.h"
 #include "posenc_kernel.h"
 #include "csp_kernel.h"
+#include "csp_head_kernel.h"
 #include "checker_kernel.h"
 
 using namespace range_hip;
@@ -150,6 +151,10 @@ struct range_ctx {
         DevBuf<float> d_params;
         DevBuf<double> d_freq;
         DevBuf<CspLayerArgs> d_layers;
+        // range_set_csp_head: the packed class_emb (csp_pack_head); range_csp_predict: a chunk's embeddings
+        int num_classes = 0;             // 0: no head
+        DevBuf<float> d_head;
+        DevBuf<float> ws_feats;
     } csp;
     // range_nearest_support: the chunks' partial (a, index) pairs of a split scan (checker_kernel.h)
     struct Checker {
@@ -1735,6 +1740,14 @@ static void (*csp_kernel_for(int m_tiles, int act))(CspArgs) {
     return csp_kernels[m_tiles - 1][act];
 }
 
+// ---- the CSP class head (csp_head_kernel.h), by tile height and output
+static void (*csp_head_kernel_for(int m_tiles, int mode))(CspHeadArgs) {
+    static void (*const csp_head_kernels[2][CSP_HEAD_MODES])(CspHeadArgs) = {
+        {csp_head_kernel<1, 0>, csp_head_kernel<1, 1>, csp_head_kernel<1, 2>},
+        {csp_head_kernel<2, 0>, csp_head_kernel<2, 1>, csp_head_kernel<2, 2>}};
+    return csp_head_kernels[m_tiles - 1][mode];
+}
+
 extern "C" {
 
 int range_set_csp(range_ctx* c, int32_t kind, const double* freq_host, int32_t F, int32_t n_layers, const int32_t* widths,
@@ -1762,6 +1775,7 @@ int range_set_csp(range_ctx* c, int32_t kind, const double* freq_host, int32_t F
     // a launch in flight on any stream may still read the parameters this call replaces
     HIP_TRY(hipDeviceSynchronize());
     c->csp.has = false;
+    c->csp.num_classes = 0;          // a head belongs to the network it was installed behind
     HIP_TRY(c->csp.d_params.upload(packed));
     HIP_TRY(c->csp.d_freq.upload(std::vector<double>(freq_host, freq_host + F)));
     std::vector<CspLayerArgs> layers;
@@ -1814,6 +1828,106 @@ int range_csp_encode_grid(range_ctx* c, const double* lonlat, int64_t B, float* 
     a.in0 = p.in0;
     a.in0_pad = p.layer[0].k_pad();
     return launch(csp_kernel_for(p.m_tiles, m.act), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
+}
+
+int range_set_csp_head(range_ctx* c, const float* class_emb, int32_t C) {
+    if (!c || !class_emb) return fail(RANGE_ERR_INVALID, "null argument");
+    if (!c->csp.has) return fail(RANGE_ERR_INVALID, "no CSP network set (range_set_csp): the head needs its num_filts");
+    const CspHeadPlan p = csp_head_plan(c->csp.plan.out_width, C, C, 1, CSP_HEAD_PROBS);
+    if (!p.valid) return fail(RANGE_ERR_INVALID, "CSP class head outside the supported envelope: %s", p.why);
+    std::vector<float> packed(p.packed_floats, 0.0f);
+    csp_pack_head(p, class_emb, packed.data());
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    HIP_TRY(hipDeviceSynchronize());         // a launch in flight may still read the head this call replaces
+    c->csp.num_classes = 0;
+    HIP_TRY(c->csp.d_head.upload(packed));
+    c->csp.num_classes = C;
+    return RANGE_OK;
+}
+
+int32_t range_csp_classes(const range_ctx* c) { return c && c->csp.has ? c->csp.num_classes : 0; }
+
+int32_t range_csp_head_cols_per_pass(const range_ctx* c) {
+    if (!c || !c->csp.has || !c->csp.num_classes) return 0;
+    return csp_head_plan(c->csp.plan.out_width, c->csp.num_classes, c->csp.num_classes, 1, CSP_HEAD_PROBS).cols_per_pass;
+}
+
+int range_csp_check_ids(range_ctx* c, const int32_t* ids_host, int32_t M) {
+    if (!c || !ids_host) return fail(RANGE_ERR_INVALID, "null argument");
+    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
+    if (M < 1) return fail(RANGE_ERR_INVALID, "M must be > 0");
+    for (int32_t i = 0; i < M; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= c->csp.num_classes)
+            return fail(RANGE_ERR_INVALID, "class id %d (entry %d) outside 0 .. %d", ids_host[i], i, c->csp.num_classes - 1);
+    return RANGE_OK;
+}
+
+int range_csp_head_grid(range_ctx* c, const float* feats, int64_t B, const int32_t* ids, int32_t M, int32_t mode,
+                        float* out, int64_t max_grid, range_stream_t stream) {
+    if (!c || !feats || !out) return fail(RANGE_ERR_INVALID, "null argument");
+    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (M < 1) return fail(RANGE_ERR_INVALID, "M must be > 0");
+    if (max_grid < 0) return fail(RANGE_ERR_INVALID, "max_grid must be >= 0");
+    if (mode < 0 || mode >= CSP_HEAD_MODES) return fail(RANGE_ERR_INVALID, "mode %d", mode);
+    if (mode == CSP_HEAD_SUM && ids) return fail(RANGE_ERR_INVALID, "SUM runs over all classes: no class ids");
+    if (!ids && M != c->csp.num_classes)
+        return fail(RANGE_ERR_INVALID, "M = %d without class ids: the head has %d classes", M, c->csp.num_classes);
+    if (reinterpret_cast<uintptr_t>(feats) % 4 || reinterpret_cast<uintptr_t>(out) % 4 || reinterpret_cast<uintptr_t>(ids) % 4)
+        return fail(RANGE_ERR_INVALID, "the device pointers must be 4-byte aligned");
+    const range_ctx::Csp& m = c->csp;
+    const CspHeadPlan p = csp_head_plan(m.plan.out_width, m.num_classes, M, B, mode, max_grid);
+    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld, M = %d: %s", (long long)B, M, p.why);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    CspHeadArgs a{};
+    a.x = feats;
+    a.w4 = reinterpret_cast<const float4*>(m.d_head.p);
+    a.ids = ids;
+    a.out = out;
+    a.B = B;
+    a.n_items = p.n_items;
+    a.K = p.num_filts;
+    a.k_groups = p.k_groups;
+    a.ld = p.ld;
+    a.M = p.M;
+    a.col_tiles = p.col_tiles;
+    a.n_chunks = p.n_chunks;
+    a.num_classes = p.num_classes;
+    a.chunks_per_item = p.chunks_per_item;
+    a.groups = p.groups;
+    return launch(csp_head_kernel_for(p.m_tiles, mode), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
+}
+
+int range_csp_head(range_ctx* c, const float* feats, int64_t B, const int32_t* ids, int32_t M, int32_t mode, float* out,
+                   range_stream_t stream) {
+    return range_csp_head_grid(c, feats, B, ids, M, mode, out, 0, stream);
+}
+
+int range_csp_predict(range_ctx* c, const double* lonlat, int64_t B, const int32_t* ids, int32_t M, int32_t mode,
+                      float* out, range_stream_t stream) {
+    if (!c || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
+    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (M < 1) return fail(RANGE_ERR_INVALID, "M must be > 0");
+    if (mode < 0 || mode >= CSP_HEAD_MODES) return fail(RANGE_ERR_INVALID, "mode %d", mode);
+    // the embeddings of a chunk of locations: at most 64 MiB, whole 64-row tiles
+    const int64_t width = c->csp.plan.out_width;
+    const int64_t chunk = std::min<int64_t>(INT64_C(1) << 16, (INT64_C(1) << 24) / width / 64 * 64);
+    {
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+        if (c->csp.ws_feats.ensure((size_t)(std::min(B, chunk) * width)) != hipSuccess)
+            return fail(RANGE_ERR_NOMEM, "out of device memory (%lld bytes of embeddings)", (long long)(std::min(B, chunk) * width * 4));
+    }
+    const int64_t out_stride = mode == CSP_HEAD_SUM ? 1 : M;
+    for (int64_t i = 0; i < B; i += chunk) {
+        const int64_t n = std::min(chunk, B - i);
+        if (int rc = range_csp_encode_grid(c, lonlat + 2 * i, n, c->csp.ws_feats.p, 0, stream)) return rc;
+        if (int rc = range_csp_head_grid(c, c->csp.ws_feats.p, n, ids, M, mode, out + i * out_stride, 0, stream)) return rc;
+    }
+    return RANGE_OK;
 }
 
 int range_csp_encode(range_ctx* c, const double* lonlat, int64_t B, float* out, range_stream_t stream) {

@@ -40,6 +40,10 @@ def load_model(model_name="RANGE+", pretrained_path=None, device="cuda", temp=No
             group to shard over (default: the world); ``row_shards`` - R < W: the 2-D layout, the
             bank row-sharded over groups of R ranks, W / R groups each serving its own queries
             (``range_amd.dist.make_layout``; default R = W).
+            ``class_head`` - True ('CSP' / 'CSP_INat' only): also load the checkpoint's class head, so that
+            ``model.loc_model(coords, class_of_interest, return_feats=False)``, ``.eval_single_class``,
+            ``.class_sum`` and ``range_amd.grid_predictor.GridPredictor`` give the classes' presence
+            probabilities (default False: the location embedding only).
     """
     if pretrained_path is None:
         raise ValueError("Please provide the pretrained model path.")      # load_model.py:31-32
@@ -61,7 +65,9 @@ def load_model(model_name="RANGE+", pretrained_path=None, device="cuda", temp=No
             args.temp = float(temp)
         if geo_temp is not None:
             args.geo_temp = float(geo_temp)
-    for opt in ("sh_eval", "sh_source", "pv_mode", "shards", "row_shards"):
+    if kwargs.get("class_head") and model_name not in ("CSP", "CSP_INat"):
+        raise ValueError("class_head= applies to the 'CSP' / 'CSP_INat' models")
+    for opt in ("sh_eval", "sh_source", "pv_mode", "shards", "row_shards", "class_head"):
         if opt in kwargs:
             setattr(args, opt, kwargs[opt])
     if kwargs.get("shards"):

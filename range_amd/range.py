@@ -355,6 +355,12 @@ class _CspLocEnc(nn.Module):
         super().__init__()
         self.spa_enc = _CspSpaEnc(p, device)
         self.num_filts = p.num_filts
+        if p.class_emb is not None:
+            # the class head (models.py:131): bias-free, frozen, a mirror like the net's tensors
+            self.class_emb = nn.Linear(p.num_filts, p.num_classes, bias=False, device="meta")
+            self.class_emb.weight = nn.Parameter(torch.as_tensor(p.class_emb, dtype=torch.float32, device=device),
+                                                 requires_grad=False)
+            self.num_classes = p.num_classes
 
 
 class CspLocationModel(nn.Module):
@@ -363,29 +369,80 @@ class CspLocationModel(nn.Module):
     (B, num_filts) float32 location embedding on the engine's GPU (``forward(coords, return_feats=True)``
     there), and whose parameters are the feed-forward net's, frozen, float32, on that GPU, under the
     reference's names (``loc_enc.spa_enc.ffn.layers.{i}.linear.weight`` ...).  As for SatCLIP they are a
-    read-only MIRROR: the arithmetic runs in the engine (csp_kernel.h) on its own packed copy.  The class and
-    user heads and the image decoder of the checkpoint are not loaded: this path never evaluates them."""
+    read-only MIRROR: the arithmetic runs in the engine (csp_kernel.h) on its own packed copy.  The user head
+    and the image decoder of the checkpoint are not loaded.  The class head (``class_emb``, models.py:135-173)
+    is loaded with ``load_model(..., class_head=True)`` only: then ``loc_enc.class_emb.weight`` joins the
+    parameters, ``num_classes`` is set, and ``forward(coords, class_of_interest, return_feats=False)``,
+    ``eval_single_class`` and ``class_sum`` run it in the engine (csp_head_kernel.h)."""
 
     def __init__(self, engine, p: CspParams):
         super().__init__()
         self.loc_enc = _CspLocEnc(p, engine.device)
         self.loc_emb_dim = p.num_filts
+        self.num_classes = p.num_classes if p.class_emb is not None else 0
         self._engine = [engine]
         engine.set_csp(p.kind, p.freq_list, p.widths, p.weights, p.biases, p.ln_gamma, p.ln_beta,
                        CSP_ACTIVATIONS[p.activation], p.skip_connection, p.use_layn)
+        if p.class_emb is not None:
+            engine.set_csp_head(p.class_emb)
         self.eval()
 
+    def _need_head(self, what: str):
+        if not self.num_classes:
+            raise NotImplementedError(f"CSP: {what} needs the class head - load_model(..., class_head=True); without it "
+                                      "only return_feats=True (the location embedding) is implemented")
+
+    @staticmethod
+    def _class_arg(class_of_interest):
+        """-> (ids or None, scalar?): an int / 0-d tensor is one class -> (B,), a 1-D sequence / tensor -> (B, M)."""
+        c = class_of_interest
+        if c is None:
+            return None, False
+        if torch.is_tensor(c):
+            if c.dim() == 0:
+                return [int(c)], True
+            return c, False
+        a = np.asarray(c)
+        if a.ndim == 0:
+            return [int(a)], True
+        return a, False
+
     @torch.no_grad()
-    def forward(self, coords, return_feats: bool = True):
-        if not return_feats:
-            raise NotImplementedError("CSP: only return_feats=True (the location embedding) is implemented")
-        return self.encode(_as_coords(coords, self._engine[0].device))
+    def forward(self, coords, class_of_interest=None, return_feats: bool = True):
+        """``return_feats=True`` (the default here: the embedding is what ``model(coords)`` is made of): the (B,
+        num_filts) embedding.  ``return_feats=False``: the reference's ``forward`` - (B, num_classes) float32
+        probabilities, with ``class_of_interest`` an int / 0-d tensor (B,), a 1-D sequence or tensor of ids (B, M)."""
+        if return_feats:
+            return self.encode(_as_coords(coords, self._engine[0].device))
+        self._need_head("return_feats=False")
+        x = _as_coords(coords, self._engine[0].device)
+        ids, scalar = self._class_arg(class_of_interest)
+        out = self._engine[0].csp_predict(x, ids, _native.CSP_HEAD_PROBS)
+        return out[:, 0] if scalar else out
 
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         """``x``: (B,2) float64 on the engine's GPU -> (B, num_filts) float32."""
         if x.shape[0] == 0:
             return torch.empty((0, self.loc_emb_dim), dtype=torch.float32, device=x.device)
         return self._engine[0].csp_encode(x)
+
+    @torch.no_grad()
+    def eval_single_class(self, feats: torch.Tensor, class_of_interest):
+        """models.py:162-173: ``feats`` (B, num_filts) float32 on the GPU -> the raw logits, no sigmoid: (B,) for
+        one class, (B, M) for a 1-D sequence or tensor of ids."""
+        self._need_head("eval_single_class")
+        ids, scalar = self._class_arg(class_of_interest)
+        if ids is None:
+            raise ValueError("eval_single_class needs a class_of_interest")
+        out = self._engine[0].csp_head(feats.contiguous(), ids, _native.CSP_HEAD_LOGITS)
+        return out[:, 0] if scalar else out
+
+    @torch.no_grad()
+    def class_sum(self, coords) -> torch.Tensor:
+        """``self(coords, return_feats=False).sum(1)`` - (B,) float32 - without the (B, num_classes) matrix: the
+        sum is formed in the kernel (float32, a fixed order)."""
+        self._need_head("class_sum")
+        return self._engine[0].csp_predict(_as_coords(coords, self._engine[0].device), None, _native.CSP_HEAD_SUM)
 
 
 class _EncoderBase(nn.Module):
@@ -494,7 +551,7 @@ class LocationEncoder(_EncoderBase):
             self._posenc = spec
         elif self.location_model_name in _CSP_MODELS:                   # range.py:140-150
             print(_CSP_MODELS[self.location_model_name])
-            csp = read_csp_checkpoint(args.pretrained_path)
+            csp = read_csp_checkpoint(args.pretrained_path, class_head=bool(getattr(args, "class_head", False)))
             self.location_feature_dim = csp.num_filts                   # (256 for the published checkpoints: :144, :150)
             self._model_id = None
             self.csp_params = csp

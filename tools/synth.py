@@ -261,7 +261,7 @@ def make_csp_checkpoint(spa_enc_type: str = "gridcell", F: int = 32, hidden: int
                         act: str = "gelu", use_layn: bool = True, skip: bool = True, num_filts: int = 256,
                         min_radius: float = 0.001, max_radius: float = 360.0, seed: int = 77,
                         freq_init: str = "geometric", num_classes: int = 5, cnn_feat_dim: int = 8,
-                        device: str = "cuda:3") -> Dict[str, object]:
+                        device: str = "cuda:3", class_scale: float = 1.0) -> Dict[str, object]:
     """A checkpoint dict with the reference's key names: ``params`` as ``get_csp`` / ``get_model`` /
     ``get_ffn`` read them and the ``state_dict`` of a ``LocationImageEncoder`` - the feed-forward net under
     ``loc_enc.spa_enc.ffn.layers.{i}.linear.*`` / ``.layernorm.*`` (float32, numpy-seeded: Xavier-uniform
@@ -269,7 +269,8 @@ def make_csp_checkpoint(spa_enc_type: str = "gridcell", F: int = 32, hidden: int
     alias, and the heads a reader of the location embedding must ignore (``class_emb``, ``user_emb``, ``img_dec``,
     each under its aliases).  ``layers``: num_hidden_layer (0: one layer from the features to num_filts).
     ``device``: ``params['device']``, the training job's - the reference moves the model there (load_csp.py:21),
-    range_amd ignores it."""
+    range_amd ignores it.  ``class_scale``: ``class_emb`` is N(0, 1) times this, applied after every draw (no
+    other tensor changes with it) - small enough, the class head's sigmoid does not saturate."""
     import torch
 
     rng = np.random.default_rng(seed)
@@ -296,6 +297,8 @@ def make_csp_checkpoint(spa_enc_type: str = "gridcell", F: int = 32, hidden: int
         sd[pre + "class_emb.weight"] = class_emb
         sd[pre + "user_emb.weight"] = user_emb
     sd["img_dec.weight"], sd["img_dec.bias"] = f32(num_filts, cnn_feat_dim), f32(num_filts)
+    if class_scale != 1.0:
+        class_emb.mul_(float(np.float32(class_scale)))        # in place: both aliases
     params = {
         "spa_enc_type": spa_enc_type, "num_loc_feats": 2, "num_classes": num_classes, "num_filts": num_filts,
         "num_users": 1, "device": device, "train_loss": "full_loss", "unsuper_loss": "contsoftmax",
