@@ -4,8 +4,12 @@
 // packed size over the envelope; every index the kernel forms (csp_kernel.h) inside the LDS image and the
 // packed parameters; every weight packed exactly once and found where the kernel's lane reads it; the tiles
 // of a launch covered exactly once, also with a capped grid and beyond 2^31 locations; the invalid cases.
+// The width lists of tests/csp_sweep_cases.py (SWEEP; `csp_plan --sweep` prints this file's copy, which
+// tests/test_csp_sweep_cpu.py compares with that table): the tile height, and the packing read back through
+// csp_packed_index - every (n, k) at an index of its own inside the layer's weights, every other float zero.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <vector>
 
@@ -81,7 +85,70 @@ static void check_tiles(const CspPlan& p, int64_t B) {
     CHECK(sum == p.n_tiles && p.tiles_of(p.n_tiles) == 0);
 }
 
-int main() {
+struct SweepCase { const char* name; int kind, F; std::vector<int> widths; bool skip, layn; int tile_rows; };
+
+static const std::vector<SweepCase>& sweep_cases() {
+    static const std::vector<SweepCase> cases = {
+        {"t32_sigmoid", PE_GRID, 3, {520, 520, 33}, true, true, 32},
+        {"t32_relu_1024", PE_THEORY, 64, {1024, 1}, false, false, 32},
+        {"t32_leaky_mixed", PE_GRID, 1, {40, 600, 600, 24}, true, true, 32},
+        {"t32_tanh_1024sq", PE_THEORY, 5, {1024, 1024, 7}, true, true, 32},
+        {"t32_gelu_513", PE_GRID, 16, {513, 31}, true, true, 32},
+        {"t64_deep9", PE_GRID, 2, {8, 8, 8, 8, 8, 8, 8, 8, 8}, true, true, 64},
+        {"t64_deep9_plain", PE_THEORY, 4, {24, 24, 24, 24, 24, 24, 24, 24, 5}, true, false, 64},
+        {"t64_mixed", PE_THEORY, 7, {512, 9, 33, 33, 512, 9}, true, true, 64},
+        {"t64_F64", PE_GRID, 64, {256, 256, 100}, true, false, 64},
+        {"t64_w1", PE_GRID, 1, {1}, false, false, 64},
+        {"saturated", PE_GRID, 8, {64, 16}, false, false, 64},
+    };
+    return cases;
+}
+
+// W[n][k] = 1 + n * in + k (exact in float32 up to 1024 x 1024) packed and read back: every (n, k) at an index of
+// its own inside [w_off, b_off), every other float of the layer's weights zero; the other layers' floats untouched
+static void check_sweep_packing(const SweepCase& c) {
+    const int n_layers = (int)c.widths.size();
+    const CspPlan p = csp_plan(c.kind, c.F, n_layers, c.widths.data(), c.skip, c.layn, 1);
+    CHECK(p.valid && p.tile_rows == c.tile_rows && p.m_tiles * 32 == c.tile_rows);
+    for (int i = 0; i < n_layers; ++i) {
+        const CspLayerPlan& l = p.layer[i];
+        std::vector<float> packed(p.packed_floats, 0.0f);
+        std::vector<float> w((size_t)l.out * l.in), b(l.out, 0.0f), g(l.out, 0.0f), be(l.out, 0.0f);
+        for (size_t j = 0; j < w.size(); ++j) w[j] = (float)(1 + j);
+        csp_pack_layer(p, i, w.data(), b.data(), g.data(), be.data(), packed.data());
+        std::vector<char> seen(p.packed_floats, 0);
+        for (int n = 0; n < l.out; ++n)
+            for (int k = 0; k < l.in; ++k) {
+                const size_t at = l.w_off + csp_packed_index(l, n, k);
+                CHECK(at >= l.w_off && at < l.b_off && !seen[at]);
+                seen[at] = 1;
+                CHECK(packed[at] == (float)(1 + (size_t)n * l.in + k));
+            }
+        for (size_t at = 0; at < p.packed_floats; ++at) CHECK(seen[at] || packed[at] == 0.0f);
+    }
+}
+
+static void print_sweep() {
+    for (const SweepCase& c : sweep_cases()) {
+        const int n_layers = (int)c.widths.size();
+        const CspPlan p = csp_plan(c.kind, c.F, n_layers, c.widths.data(), c.skip, c.layn, 1);
+        std::printf("%s kind=%s F=%d skip=%d layn=%d T=%d layers=%d widths=", c.name, c.kind == PE_GRID ? "gridcell" : "theory",
+                    c.F, (int)c.skip, (int)c.layn, p.tile_rows, n_layers);
+        for (int i = 0; i < n_layers; ++i) std::printf("%s%d", i ? "," : "", c.widths[i]);
+        std::printf(" ntw=");        // column tiles of wave 0 (the largest share) per layer
+        for (int i = 0; i < n_layers; ++i) std::printf("%s%d", i ? "," : "", (p.layer[i].n_tiles + 3) / 4);
+        std::printf(" idle_waves=");
+        for (int i = 0; i < n_layers; ++i) std::printf("%s%d", i ? "," : "", std::max(0, 4 - p.layer[i].n_tiles));
+        std::printf("\n");
+    }
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "--sweep")) { print_sweep(); return 0; }
+    for (const SweepCase& c : sweep_cases()) {
+        check_network(c.kind, c.F, c.widths, c.skip, c.layn);
+        check_sweep_packing(c);
+    }
     for (int kind : {PE_GRID, PE_THEORY})
         for (int F : {1, 5, 16, 32, 64})
             for (bool skip : {false, true})

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import csp_refs as R
+from csp_sweep_cases import torch_f32
 from range_amd import _native, csp, posenc
 from tools import synth
 
@@ -101,21 +102,6 @@ def wide_network(seed=301):
                 weights=[t(i, "linear.weight") for i in range(3)], biases=[t(i, "linear.bias") for i in range(3)],
                 ln_gamma=[t(0, "layernorm.weight"), t(1, "layernorm.weight"), None],
                 ln_beta=[t(0, "layernorm.bias"), t(1, "layernorm.bias"), None])
-
-
-def torch_f32(net, feat32):
-    """The network on torch's float32 CPU operators, as module.py composes them."""
-    import torch.nn.functional as F
-    x = torch.from_numpy(feat32)
-    n = len(net["weights"])
-    for i in range(n):
-        y = F.gelu(F.linear(x, torch.from_numpy(net["weights"][i]), torch.from_numpy(net["biases"][i])))
-        if i + 1 < n:
-            if y.shape == x.shape:
-                y = y + x
-            y = F.layer_norm(y, (y.shape[1],), torch.from_numpy(net["ln_gamma"][i]), torch.from_numpy(net["ln_beta"][i]))
-        x = y
-    return x.numpy()
 
 
 def test_the_32_row_tile(engine):
