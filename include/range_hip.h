@@ -282,6 +282,38 @@ int range_csp_head_grid(range_ctx* ctx, const float* feats_dev, int64_t B, const
 int range_csp_predict(range_ctx* ctx, const double* lonlat_dev, int64_t B, const int32_t* class_ids_dev, int32_t M,
                       int32_t mode, float* out_dev, range_stream_t stream);
 
+/* The evaluation that head exists for (csp/main/eval_helper.py: compute_acc_batch / get_label_rank) without the
+ * (B, C) matrix (csp_rank_kernel.h): per row b with label t, over the scores s_c = (double) p_c * (double)
+ * img[b, c] of ALL C classes - p_c the bits range_csp_head(PROBS) gives; without image predictions s_c = (double)
+ * p_c; without embeddings (the reference's prior_type = 'no_prior') s_c = (double) img[b, c] -
+ *   greater[b]    : classes c != t with s_c > s_t or s_c NaN
+ *   tied_after[b] : classes c > t with s_c == s_t
+ *   argmax[b]     : the first index of the maximum, the first NaN if there is one (np.argmax)
+ * The rank of the label is 1 + greater + tied_after: np.argsort(kind = 'stable')[:, ::-1] followed by the
+ * reference's second argsort (the reference's default sort leaves the order among exact ties unspecified; this
+ * is the rule here).  All three are -1 where s_t is NaN (a NaN / infinite location row, which the reference drops)
+ * and -2 where the label is outside [0, C) (nothing out of bounds is read).
+ * range_csp_rank: feats_dev (B, num_filts) float32 or NULL, img_dev (B, C) of img_kind or NULL (RANGE_CSP_IMG_NONE),
+ * labels_dev (B) int32 -> three (B) int32 arrays.  RANGE_ERR_INVALID: no head installed, a null output, feats and
+ * img both NULL, img_kind not matching img_dev, B outside the head's range.
+ * range_csp_rank_grid: at most max_grid workgroups (0: the default cap), the classes split into col_parts parts
+ * (0: the plan's choice; at most the plan's chunks); same bits.  For tests.
+ * range_csp_predict_rank: lonlat_dev (B,2) float64 -> range_csp_encode into the context's workspace in the chunks
+ * of range_csp_predict, then range_csp_rank: the same bits as the two calls.  One rank call per context at a time
+ * (the workspaces are the context's). */
+#define RANGE_CSP_IMG_NONE 0
+#define RANGE_CSP_IMG_F32 1
+#define RANGE_CSP_IMG_F64 2
+int range_csp_rank(range_ctx* ctx, const float* feats_dev, int64_t B, const void* img_dev, int32_t img_kind,
+                   const int32_t* labels_dev, int32_t* greater_dev, int32_t* tied_after_dev, int32_t* argmax_dev,
+                   range_stream_t stream);
+int range_csp_rank_grid(range_ctx* ctx, const float* feats_dev, int64_t B, const void* img_dev, int32_t img_kind,
+                        const int32_t* labels_dev, int32_t* greater_dev, int32_t* tied_after_dev, int32_t* argmax_dev,
+                        int64_t max_grid, int32_t col_parts, range_stream_t stream);
+int range_csp_predict_rank(range_ctx* ctx, const double* lonlat_dev, int64_t B, const void* img_dev, int32_t img_kind,
+                           const int32_t* labels_dev, int32_t* greater_dev, int32_t* tied_after_dev,
+                           int32_t* argmax_dev, range_stream_t stream);
+
 /* The checkerboard task's nearest support point (the reference's evaluation/checkerboarddataset.py:78-107:
  * assign_closest_label; :175-194: the nearest-neighbour statistic) as one scan (checker_kernel.h).  For every
  * query i the support j with the smallest haversine term

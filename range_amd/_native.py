@@ -26,6 +26,7 @@ PROF_ENCODER, PROF_SCAN_STATS, PROF_ATTEND, PROF_TOPK_STREAM, PROF_TOPK_MERGE, P
 COORD_DIRECT, COORD_CARTESIAN3D, COORD_WRAP = 0, 1, 2   # range_coord_features(mode)
 COORD_DIMS = {COORD_DIRECT: 2, COORD_CARTESIAN3D: 3, COORD_WRAP: 4}
 CSP_HEAD_PROBS, CSP_HEAD_LOGITS, CSP_HEAD_SUM = 0, 1, 2   # range_csp_head(mode)
+CSP_IMG_NONE, CSP_IMG_F32, CSP_IMG_F64 = 0, 1, 2            # range_csp_rank(img_kind)
 
 # every symbol include/range_hip.h declares
 SYMBOLS = (
@@ -43,7 +44,7 @@ SYMBOLS = (
     "range_posenc_width", "range_posenc_features",
     "range_set_csp", "range_csp_width", "range_csp_tile_rows", "range_csp_encode", "range_csp_encode_grid",
     "range_set_csp_head", "range_csp_classes", "range_csp_head_cols_per_pass", "range_csp_check_ids", "range_csp_head",
-    "range_csp_head_grid", "range_csp_predict",
+    "range_csp_head_grid", "range_csp_predict", "range_csp_rank", "range_csp_rank_grid", "range_csp_predict_rank",
     "range_nearest_support",
 )
 PV_MODES = {"exact": 0, "bf16x3": 1}   # range_set_pv_mode
@@ -135,6 +136,9 @@ def load_library() -> C.CDLL:
     lib.range_csp_head.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp]
     lib.range_csp_head_grid.argtypes = [vp, vp, i64, vp, i32, i32, vp, i64, vp]
     lib.range_csp_predict.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp]
+    lib.range_csp_rank.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    lib.range_csp_rank_grid.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp, i64, i32, vp]
+    lib.range_csp_predict_rank.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp, vp]
     lib.range_nearest_support.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     lib.range_set_pv_mode.argtypes = [vp, i32]
     lib.range_get_pv_mode.argtypes = [vp]
@@ -489,6 +493,54 @@ class HipEngine:
         if B:
             _check(self.lib, self.lib.range_csp_predict(self._h, lonlat.data_ptr(), B, _ptr(dev_ids), M, int(mode),
                                                         out.data_ptr(), self._stream()))
+        return out
+
+    def _csp_rank_args(self, B: int, img: Optional[torch.Tensor], labels: torch.Tensor):
+        C_ = self.csp_classes
+        if C_ <= 0:
+            raise RangeNativeError("no CSP class head set on this engine (set_csp_head)")
+        self._t(labels, torch.int32, ())
+        if labels.shape[0] != B:
+            raise ValueError(f"{labels.shape[0]} labels for {B} rows")
+        kind = CSP_IMG_NONE
+        if img is not None:
+            if img.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"image predictions must be float32 or float64, got {img.dtype}")
+            self._t(img, img.dtype, (C_,))
+            if img.shape[0] != B:
+                raise ValueError(f"{img.shape[0]} rows of image predictions for {B} rows")
+            kind = CSP_IMG_F32 if img.dtype == torch.float32 else CSP_IMG_F64
+        return kind, tuple(self._empty((B,), torch.int32) for _ in range(3))
+
+    def csp_rank(self, feats: Optional[torch.Tensor], labels: torch.Tensor, img: Optional[torch.Tensor] = None,
+                 max_grid: int = 0, col_parts: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The evaluation behind the class head (range_csp_rank): ``feats`` (B, num_filts) float32 or None,
+        ``labels`` (B,) int32, ``img`` (B, num_classes) float32 / float64 image predictions or None -> (``greater``,
+        ``tied_after``, ``argmax``), (B,) int32 each, over the scores ``p.double() * img.double()`` of all classes.
+        The label's rank is ``1 + greater + tied_after``; all three are -1 where the label's score is NaN, -2 where
+        the label is outside ``[0, num_classes)``.  ``max_grid`` / ``col_parts``: range_csp_rank_grid (tests)."""
+        if feats is None and img is None:
+            raise ValueError("csp_rank needs embeddings, image predictions or both")
+        if feats is not None:
+            self._t(feats, torch.float32, (self.lib.range_csp_width(self._h),))
+        B = labels.shape[0] if feats is None else feats.shape[0]
+        kind, out = self._csp_rank_args(B, img, labels)
+        if B:
+            _check(self.lib, self.lib.range_csp_rank_grid(self._h, _ptr(feats), B, _ptr(img), kind, labels.data_ptr(),
+                                                          out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                          int(max_grid), int(col_parts), self._stream()))
+        return out
+
+    def csp_predict_rank(self, lonlat: torch.Tensor, labels: torch.Tensor,
+                         img: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Encoder, class head and ``csp_rank`` in one call (range_csp_predict_rank): ``lonlat`` (B,2) float64 degrees."""
+        self._t(lonlat, torch.float64, (2,))
+        B = lonlat.shape[0]
+        kind, out = self._csp_rank_args(B, img, labels)
+        if B:
+            _check(self.lib, self.lib.range_csp_predict_rank(self._h, lonlat.data_ptr(), B, _ptr(img), kind,
+                                                             labels.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                                             out[2].data_ptr(), self._stream()))
         return out
 
     def nearest_support(self, q_rad: torch.Tensor, s_rad: torch.Tensor, exclude_self: bool = False, max_chunks: int = 0,

@@ -1,0 +1,123 @@
+"""The evaluation of the CSP "geo prior" (reference: location_models/csp/main/eval_helper.py ``compute_acc_batch``
+/ ``get_label_rank``): the rank of the true class among ``image prediction * geo prior``, top-1/3/5/10 accuracy
+per split, the predicted classes.
+
+The rank rule, here and in the kernel (csrc/csp_rank_kernel.h): with scores ``s`` (float64) and label ``t``
+
+    rank = 1 + #{c != t : s_c > s_t or s_c is NaN} + #{c > t : s_c == s_t}
+
+which is what ``np.argsort(s, kind='stable')[:, ::-1]`` followed by the reference's second argsort gives (NaN
+sorts last in numpy, so first after the reversal; among equal scores the reversal puts the later class first).
+The reference's own ``np.argsort`` is the default, unstable sort: among exact ties its order is unspecified, on
+tie-free rows it is this rule.  The predicted class is ``np.argmax``: the first index of the maximum, the first
+NaN if there is one.  A row whose label's score is NaN has no rank: 0 here, predicted class -1.
+
+numpy only: importable, and testable, without a GPU.  ``compute_acc_batch`` with a CSP prior runs
+``CspLocationModel.label_ranks`` - one kernel launch per chunk, three integers per sample, no (B, num_classes)
+matrix."""
+from __future__ import annotations
+
+import logging
+from typing import List, Tuple
+
+import numpy as np
+
+TOP_KS = (1, 3, 5, 10)
+#: prior types of eval_helper.py this module does not serve
+UNSUPPORTED_PRIORS = ("train_freq", "nn_dist", "nn_knn", "kde", "grid", "tang_et_al")
+
+
+def rank_counts(scores, labels) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The kernel's three outputs on a host matrix: ``scores`` (B, C) floats, ``labels`` (B,) integers ->
+    (``greater``, ``tied_after``, ``argmax``) int32 (B,) each; all three -1 where the label's score is NaN, -2 where
+    the label is outside ``[0, C)``."""
+    s = np.asarray(scores)
+    lab = np.asarray(labels).astype(np.int64)
+    if s.ndim != 2 or lab.shape != (s.shape[0],):
+        raise ValueError(f"scores (B, C) and labels (B,), got {s.shape} and {lab.shape}")
+    B, C = s.shape
+    out = np.zeros((3, B), dtype=np.int32)
+    cols = np.arange(C)
+    for i in range(0, B, 256):
+        blk, t = s[i:i + 256].astype(np.float64), lab[i:i + 256]
+        bad = (t < 0) | (t >= C)
+        tc = np.where(bad, 0, t)
+        st = blk[np.arange(len(t)), tc][:, None]
+        with np.errstate(invalid="ignore"):
+            greater = (~(blk <= st)) & (cols[None, :] != tc[:, None])
+            tied = (blk == st) & (cols[None, :] > tc[:, None])
+        res = np.stack([greater.sum(1), tied.sum(1), np.argmax(blk, axis=1)]).astype(np.int32)
+        res[:, np.isnan(st[:, 0])] = -1
+        res[:, bad] = -2
+        out[:, i:i + 256] = res
+    return out[0], out[1], out[2]
+
+
+def get_label_rank(loc_pred, loc_class) -> np.ndarray:
+    """eval_helper.py ``get_label_rank``: ``loc_pred`` (B, C) scores, ``loc_class`` (B,) labels -> (B,) int64 ranks
+    from 1 by the rule of this module; 0 where the label's score is NaN.  ValueError: a label outside ``[0, C)``."""
+    g, e, _ = rank_counts(loc_pred, loc_class)
+    if (g == -2).any():
+        raise ValueError(f"labels outside 0 .. {np.asarray(loc_pred).shape[1] - 1}")
+    return np.where(g < 0, 0, 1 + g.astype(np.int64) + e.astype(np.int64))
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def compute_acc_batch(val_preds, val_classes, val_split, val_feats=None, train_classes=None, train_feats=None,
+                      prior_type="no_prior", prior=None, hyper_params=None, batch_size=1024, logger=None,
+                      eval_flag_str="", return_acc=False):
+    """eval_helper.py ``compute_acc_batch``.  ``val_preds``: (N, num_classes) image predictions, float32 or
+    float64, or None (the location-only accuracy); ``val_classes`` (N,) labels; ``val_split`` (N,) split ids;
+    ``val_feats``: (N, 2) (lon, lat) DEGREES, as ``model(coords)`` takes them (the reference passes what its own
+    data loader normalised).  ``prior_type='no_prior'`` ranks ``val_preds`` alone; ``prior`` a ``CspLocationModel``
+    loaded with ``class_head=True`` and ``prior_type`` its ``spa_enc_type`` or ``'geo_net'`` ranks ``val_preds *
+    prior(val_feats)``, ``batch_size`` rows a call; any other ``prior_type`` raises NotImplementedError.  Logs the
+    reference's ``Top k acc (%)`` lines per split with its denominators (a sample the reference drops - no
+    location - is a miss over the whole split) and returns its list of predicted classes, of the samples it keeps;
+    with ``return_acc=True`` also ``{split: {k: accuracy in per cent}}``."""
+    logger = logger or logging.getLogger(__name__)
+    val_classes, val_split = _host(val_classes).reshape(-1), _host(val_split).reshape(-1)
+    N = len(val_classes)
+    if prior_type == "no_prior":
+        if val_preds is None:
+            raise ValueError("prior_type='no_prior' needs val_preds")
+        ranks = np.zeros(N, dtype=np.int64)
+        pred = np.full(N, -1, dtype=np.int64)
+        for i in range(0, N, batch_size):
+            blk = _host(val_preds[i:i + batch_size])
+            g, e, _ = rank_counts(blk, val_classes[i:i + batch_size])
+            if (g == -2).any():
+                raise ValueError("val_classes outside the classes of val_preds")
+            ok = g >= 0
+            ranks[i:i + batch_size][ok] = 1 + g[ok].astype(np.int64) + e[ok]
+            pred[i:i + batch_size] = np.argmax(blk, axis=1)          # 'no_prior' drops no row
+        kept = np.ones(N, dtype=bool)
+    elif prior is not None and hasattr(prior, "label_ranks") and \
+            prior_type in ("geo_net", getattr(prior, "spa_enc_type", "geo_net")):
+        if val_feats is None:
+            raise ValueError(f"prior_type={prior_type!r} needs val_feats, the (lon, lat) degrees")
+        ranks = np.zeros(N, dtype=np.int64)
+        pred = np.full(N, -1, dtype=np.int64)
+        for i in range(0, N, batch_size):
+            sl = slice(i, min(N, i + batch_size))
+            ranks[sl], pred[sl] = prior.label_ranks(val_feats[sl], val_classes[sl],
+                                                    None if val_preds is None else val_preds[sl])
+        kept = ranks > 0
+    else:
+        raise NotImplementedError(f"compute_acc_batch: prior_type={prior_type!r} is not implemented (only 'no_prior' and "
+                                  "a CSP prior: 'geo_net' or the model's spa_enc_type with prior a CspLocationModel)")
+    logger.info(val_classes[kept].shape)
+    acc = {}
+    for ii, split in enumerate(np.unique(val_split)):
+        logger.info(" Split ID: {}".format(ii))
+        inds1 = np.where(val_split == split)[0]
+        acc[split.item() if hasattr(split, "item") else split] = row = {}
+        for kk in TOP_KS:
+            hits = int(((ranks[inds1] >= 1) & (ranks[inds1] <= kk)).sum())
+            row[kk] = round(hits * 100 / len(inds1), 2)
+            logger.info(" Top {}\t{}acc (%):   {}".format(kk, eval_flag_str, row[kk]))
+    pred_classes: List[int] = list(pred[kept])
+    return (pred_classes, acc) if return_acc else pred_classes

@@ -99,6 +99,48 @@ __device__ __forceinline__ void csp_head_gemm_dispatch(csp_f32x16 (&acc)[MT][NT]
     else if constexpr (NTW > 1) csp_head_gemm_dispatch<MT, NT, NTW - 1>(acc, ntw, w4, base, k_groups, xa, m_stride);
 }
 
+// The X tile: rows b0 .. b0 + T - 1 of x (B, K) into `hx`, row stride ld, columns K .. k_pad - 1 and rows beyond
+// B zero.  Wave w loads rows w, w + 4, ...; a lane the columns lane, lane + 64, ... (16 bytes each where vec4:
+// every row starts 16-byte aligned - K % 4 == 0: then k_pad % 4 == 0 and K..k_pad is whole float4s).
+template <int T>
+__device__ __forceinline__ void csp_head_load_x(const float* x, int64_t B, int64_t b0, int K, int k_pad, int ld, bool vec4,
+                                                float* hx, int wave, int lane) {
+    if (vec4) {
+#pragma unroll 4
+        for (int r = wave; r < T; r += 4) {
+            const bool live = b0 + r < B;
+            const float4* const src = reinterpret_cast<const float4*>(x + (b0 + r) * K);
+            for (int k4 = lane; 4 * k4 < k_pad; k4 += 64) {
+                const float4 v = live && 4 * k4 < K ? src[k4] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+                float* const dst = hx + r * ld + 4 * k4;
+                dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int r = wave; r < T; r += 4) {
+            const bool live = b0 + r < B;
+            for (int k = lane; k < k_pad; k += 64) hx[r * ld + k] = live && k < K ? x[(b0 + r) * K + k] : 0.0f;
+        }
+    }
+}
+
+// The columns of a wave's tiles t0, t0 + 4, ...: col[j] the lane's column of the call, base[j] the float4 index of
+// its class's fragment of k group 0 in the packed class_emb (csp_packed_index of the id, the lane's k parity lh).
+template <int NT>
+__device__ __forceinline__ void csp_head_columns(uint32_t (&base)[NT], int (&col)[NT], int t0, int l31, int lh,
+                                                 const int32_t* ids, int M, int num_classes, int k_groups) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int c = (t0 + 4 * j) * 32 + l31;
+        const int cc = c < M ? c : M - 1;
+        int id = ids ? ids[cc] : cc;
+        id = id < 0 ? 0 : id < num_classes ? id : num_classes - 1;     // (a bad device id reads class 0 / C - 1)
+        col[j] = c;
+        base[j] = ((uint32_t)(id >> 5) * (uint32_t)k_groups) * 64u + 32u * lh + (uint32_t)(id & 31);
+    }
+}
+
 template <int MT, int MODE>
 __global__ __launch_bounds__(CSP_BLOCK, 2) void csp_head_kernel(CspHeadArgs a) {
     constexpr int T = 32 * MT;                  // rows of a tile
@@ -109,7 +151,7 @@ __global__ __launch_bounds__(CSP_BLOCK, 2) void csp_head_kernel(CspHeadArgs a) {
     const int l31 = lane & 31, lh = lane >> 5;
     const int ld = a.ld, K = a.K, k_pad = a.k_groups * 8;
     float* const part = csp_hx + T * ld;        // SUM: (4 waves, T) partial row sums
-    // 16-byte loads of X: every row starts 16-byte aligned (K % 4 == 0: then k_pad % 4 == 0 and K..k_pad is whole float4s)
+    // 16-byte loads of X: every row starts 16-byte aligned
     const bool vec4 = K % 4 == 0 && reinterpret_cast<uintptr_t>(a.x) % 16 == 0;
     int64_t loaded = -1;
     for (int64_t item = blockIdx.x; item < a.n_items; item += gridDim.x) {
@@ -119,25 +161,7 @@ __global__ __launch_bounds__(CSP_BLOCK, 2) void csp_head_kernel(CspHeadArgs a) {
         const int64_t b0 = rt * T;
         if (rt != loaded) {
             __syncthreads();                    // the last item's reads of the tile (and of `part`) are done
-            // wave w loads rows w, w + 4, ...; a lane the columns lane, lane + 64, ... (16 bytes each where it can)
-            if (vec4) {
-#pragma unroll 4
-                for (int r = wave; r < T; r += 4) {
-                    const bool live = b0 + r < a.B;
-                    const float4* const src = reinterpret_cast<const float4*>(a.x + (b0 + r) * K);
-                    for (int k4 = lane; 4 * k4 < k_pad; k4 += 64) {
-                        const float4 v = live && 4 * k4 < K ? src[k4] : float4{0.0f, 0.0f, 0.0f, 0.0f};
-                        float* const dst = csp_hx + r * ld + 4 * k4;
-                        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
-                    }
-                }
-            } else {
-#pragma unroll 4
-                for (int r = wave; r < T; r += 4) {
-                    const bool live = b0 + r < a.B;
-                    for (int k = lane; k < k_pad; k += 64) csp_hx[r * ld + k] = live && k < K ? a.x[(b0 + r) * K + k] : 0.0f;
-                }
-            }
+            csp_head_load_x<T>(a.x, a.B, b0, K, k_pad, ld, vec4, csp_hx, wave, lane);
             __syncthreads();
             loaded = rt;
         }
@@ -156,15 +180,7 @@ __global__ __launch_bounds__(CSP_BLOCK, 2) void csp_head_kernel(CspHeadArgs a) {
             if (ntw == 0) continue;
             uint32_t base[NT];
             int col[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int c = (t0 + 4 * j) * 32 + l31;
-                const int cc = c < a.M ? c : a.M - 1;
-                int id = a.ids ? a.ids[cc] : cc;
-                id = id < 0 ? 0 : id < a.num_classes ? id : a.num_classes - 1;     // (a bad device id reads class 0 / C - 1)
-                col[j] = c;
-                base[j] = ((uint32_t)(id >> 5) * (uint32_t)a.k_groups) * 64u + 32u * lh + (uint32_t)(id & 31);
-            }
+            csp_head_columns<NT>(base, col, t0, l31, lh, a.ids, a.M, a.num_classes, a.k_groups);
             csp_f32x16 acc[MT][NT];
 #pragma unroll
             for (int m = 0; m < MT; ++m)

@@ -848,6 +848,84 @@ inline void csp_pack_head(const CspHeadPlan& p, const float* class_emb, float* d
         for (int k = 0; k < p.num_filts; ++k) dst[csp_packed_index(l, n, k)] = class_emb[(size_t)n * p.num_filts + k];
 }
 
+// The evaluation behind the class head (csp_rank_kernel.h; range_csp_rank): per row the true class's rank counts
+// and the arg-max of s_c = p_c * img[b, c] over ALL classes, the head's tile and chunks (csp_head_plan in PROBS
+// mode, M = num_classes) with the image predictions read where the head would store.  A work item is a row tile
+// with one of `col_parts` consecutive, balanced shares of the chunks: item = row tile * col_parts + part.  The
+// row tiles alone fill the chip from CSP_RANK_TARGET_WG on (256 CUs x 2 workgroups); below that col_parts is the
+// smallest number of parts that reaches it, at most one part a chunk.  With more than one part the partial
+// (greater, tied_after, best score, best index) take col_parts * B * 20 bytes of workspace and a merge launch
+// follows.  Without embeddings (has_head = false: the reference's 'no_prior') no X tile is held and the tile is
+// 64 rows.  LDS behind the X tile, per row: four waves' {s_t, best} (16 bytes each), s_t (8), four waves' best
+// index, greater and tied counts (4 bytes each), the label (4).
+enum { CSP_IMG_NONE = 0, CSP_IMG_F32 = 1, CSP_IMG_F64 = 2, CSP_IMG_KINDS = 3 };
+constexpr int64_t CSP_RANK_TARGET_WG = 512;
+constexpr size_t CSP_RANK_ROW_STATE = 4 * 16 + 8 + 3 * 4 * 4 + 4;     // bytes of LDS a row beside the X tile
+constexpr size_t CSP_RANK_WS_ROW = 8 + 3 * 4;                         // bytes of workspace a row and part
+
+struct CspRankPlan {
+    bool valid = false;
+    const char* why = "";
+    int num_filts = 0, num_classes = 0, img_kind = 0;
+    bool has_head = false;
+    int tile_rows = 0, m_tiles = 0, ld = 0, k_groups = 0;
+    int wave_tiles = 0, cols_per_pass = 0, col_tiles = 0;
+    int n_chunks = 0;                    // ceil(num_classes / cols_per_pass)
+    int col_parts = 0;
+    int64_t row_tiles = 0, n_items = 0;
+    size_t lds_bytes = 0, ws_bytes = 0;  // ws_bytes: 0 with one part
+    unsigned grid = 0, merge_grid = 0;   // merge_grid: 0 with one part
+    int block = CSP_BLOCK;
+    int64_t items_of(int64_t blk) const { return blk < n_items ? (n_items - blk + grid - 1) / grid : 0; }
+    // item -> its row tile, its part and the part's chunks [chunk0, chunk1)
+    void item(int64_t it, int64_t& row_tile, int& part, int& chunk0, int& chunk1) const {
+        row_tile = it / col_parts;
+        part = (int)(it - row_tile * col_parts);
+        chunk0 = (int)((int64_t)part * n_chunks / col_parts);
+        chunk1 = (int)((int64_t)(part + 1) * n_chunks / col_parts);
+    }
+    // the column tiles wave `w` (0 .. 3) sweeps in chunk `ch`: the first, and how many (stride 4) - the head's
+    int wave_first_tile(int ch, int w) const { return ch * 4 * wave_tiles + w; }
+    int wave_n_tiles(int ch, int w) const {
+        const int t0 = wave_first_tile(ch, w);
+        return col_tiles > t0 ? std::min(wave_tiles, (col_tiles - t0 + 3) / 4) : 0;
+    }
+};
+
+// img_kind: CSP_IMG_*.  has_head: embeddings are given.  max_grid: a smaller cap than CSP_MAX_GRID (0: none).
+// col_parts: 0 the plan's choice, n > 0 exactly n parts.
+inline CspRankPlan csp_rank_plan(int num_filts, int num_classes, int64_t B, int img_kind, bool has_head,
+                                 int64_t max_grid = 0, int col_parts = 0) {
+    CspRankPlan p;
+    if (img_kind < 0 || img_kind >= CSP_IMG_KINDS) { p.why = "img_kind (NONE, F32 or F64)"; return p; }
+    if (!has_head && img_kind == CSP_IMG_NONE) { p.why = "neither embeddings nor image predictions"; return p; }
+    if (col_parts < 0) { p.why = "col_parts below 0"; return p; }
+    const CspHeadPlan h = csp_head_plan(num_filts, num_classes, num_classes, B, CSP_HEAD_PROBS, max_grid);
+    if (!h.valid) { p.why = h.why; return p; }
+    p.num_filts = num_filts; p.num_classes = num_classes; p.img_kind = img_kind; p.has_head = has_head;
+    p.m_tiles = has_head ? h.m_tiles : 2;
+    p.tile_rows = 32 * p.m_tiles;
+    p.k_groups = h.k_groups;
+    p.ld = h.ld;
+    p.wave_tiles = CSP_HEAD_ACC_TILES / p.m_tiles;
+    p.cols_per_pass = 4 * p.wave_tiles * CSP_NTILE;
+    p.col_tiles = h.col_tiles;
+    p.n_chunks = (num_classes + p.cols_per_pass - 1) / p.cols_per_pass;
+    if (col_parts > p.n_chunks) { p.why = "col_parts above the number of chunks"; return p; }
+    p.row_tiles = (B + p.tile_rows - 1) / p.tile_rows;
+    p.col_parts = col_parts ? col_parts
+                            : (int)std::min<int64_t>(p.n_chunks, (CSP_RANK_TARGET_WG + p.row_tiles - 1) / p.row_tiles);
+    p.n_items = p.row_tiles * p.col_parts;
+    p.lds_bytes = (has_head ? (size_t)p.tile_rows * p.ld * sizeof(float) : 0) + (size_t)p.tile_rows * CSP_RANK_ROW_STATE;
+    p.grid = (unsigned)std::min(p.n_items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID);
+    if (p.col_parts > 1) {
+        p.ws_bytes = (size_t)p.col_parts * (size_t)B * CSP_RANK_WS_ROW;
+        p.merge_grid = (unsigned)std::min<int64_t>((B + CSP_BLOCK - 1) / CSP_BLOCK, CSP_MAX_GRID);
+    }
+    p.valid = true;
+    return p;
+}
+
 // The nearest-support scan of the checkerboard task (checker_kernel.h; range_nearest_support): one thread per
 // query, workgroups of CHECKER_BLOCK queries (grid x, walked grid-stride), support tiles of CHECKER_TILE points
 // in LDS (lon, lat, cos lat: 3 doubles a point), the tiles dealt round-robin to `chunks` workgroups per query

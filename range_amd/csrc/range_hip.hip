@@ -30,6 +30,7 @@
 #include "posenc_kernel.h"
 #include "csp_kernel.h"
 #include "csp_head_kernel.h"
+#include "csp_rank_kernel.h"
 #include "checker_kernel.h"
 
 using namespace range_hip;
@@ -155,6 +156,8 @@ struct range_ctx {
         int num_classes = 0;             // 0: no head
         DevBuf<float> d_head;
         DevBuf<float> ws_feats;
+        // range_csp_rank: the parts' partial results of a split sweep (csp_rank_kernel.h), in doubles
+        DevBuf<double> ws_rank;
     } csp;
     // range_nearest_support: the chunks' partial (a, index) pairs of a split scan (checker_kernel.h)
     struct Checker {
@@ -1748,6 +1751,16 @@ static void (*csp_head_kernel_for(int m_tiles, int mode))(CspHeadArgs) {
     return csp_head_kernels[m_tiles - 1][mode];
 }
 
+// ---- the evaluation behind the head (csp_rank_kernel.h), by tile height, image predictions and embeddings
+static void (*csp_rank_kernel_for(int m_tiles, int img_kind, bool has_head))(CspRankArgs) {
+    static void (*const with_head[2][CSP_IMG_KINDS])(CspRankArgs) = {
+        {csp_rank_kernel<1, 0, true>, csp_rank_kernel<1, 1, true>, csp_rank_kernel<1, 2, true>},
+        {csp_rank_kernel<2, 0, true>, csp_rank_kernel<2, 1, true>, csp_rank_kernel<2, 2, true>}};
+    static void (*const without[CSP_IMG_KINDS])(CspRankArgs) = {nullptr, csp_rank_kernel<2, 1, false>,
+                                                                csp_rank_kernel<2, 2, false>};
+    return has_head ? with_head[m_tiles - 1][img_kind] : without[img_kind];
+}
+
 extern "C" {
 
 int range_set_csp(range_ctx* c, int32_t kind, const double* freq_host, int32_t F, int32_t n_layers, const int32_t* widths,
@@ -1926,6 +1939,94 @@ int range_csp_predict(range_ctx* c, const double* lonlat, int64_t B, const int32
         const int64_t n = std::min(chunk, B - i);
         if (int rc = range_csp_encode_grid(c, lonlat + 2 * i, n, c->csp.ws_feats.p, 0, stream)) return rc;
         if (int rc = range_csp_head_grid(c, c->csp.ws_feats.p, n, ids, M, mode, out + i * out_stride, 0, stream)) return rc;
+    }
+    return RANGE_OK;
+}
+
+int range_csp_rank_grid(range_ctx* c, const float* feats, int64_t B, const void* img, int32_t img_kind, const int32_t* labels,
+                        int32_t* greater, int32_t* tied_after, int32_t* argmax, int64_t max_grid, int32_t col_parts,
+                        range_stream_t stream) {
+    if (!c || !labels || !greater || !tied_after || !argmax) return fail(RANGE_ERR_INVALID, "null argument");
+    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
+    if (!feats && !img) return fail(RANGE_ERR_INVALID, "neither embeddings nor image predictions");
+    if (img_kind < 0 || img_kind >= CSP_IMG_KINDS) return fail(RANGE_ERR_INVALID, "img_kind %d", img_kind);
+    if ((img != nullptr) != (img_kind != CSP_IMG_NONE))
+        return fail(RANGE_ERR_INVALID, "img_kind %d %s image predictions", img_kind, img ? "with" : "without");
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (max_grid < 0 || col_parts < 0) return fail(RANGE_ERR_INVALID, "max_grid and col_parts must be >= 0");
+    if (reinterpret_cast<uintptr_t>(feats) % 4 || reinterpret_cast<uintptr_t>(labels) % 4 ||
+        reinterpret_cast<uintptr_t>(greater) % 4 || reinterpret_cast<uintptr_t>(tied_after) % 4 ||
+        reinterpret_cast<uintptr_t>(argmax) % 4 || reinterpret_cast<uintptr_t>(img) % (img_kind == CSP_IMG_F64 ? 8 : 4))
+        return fail(RANGE_ERR_INVALID, "the device pointers must be aligned to their element");
+    range_ctx::Csp& m = c->csp;
+    const CspRankPlan p = csp_rank_plan(m.plan.out_width, m.num_classes, B, img_kind, feats != nullptr, max_grid, col_parts);
+    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld, col_parts = %d: %s", (long long)B, col_parts, p.why);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    CspRankArgs a{};
+    a.x = feats;
+    a.w4 = reinterpret_cast<const float4*>(m.d_head.p);
+    a.img = img;
+    a.labels = labels;
+    a.greater = greater;
+    a.tied = tied_after;
+    a.argmax = argmax;
+    a.B = B;
+    a.n_items = p.n_items;
+    a.K = p.num_filts;
+    a.k_groups = p.k_groups;
+    a.ld = p.ld;
+    a.C = p.num_classes;
+    a.col_tiles = p.col_tiles;
+    a.n_chunks = p.n_chunks;
+    a.col_parts = p.col_parts;
+    if (p.col_parts > 1) {
+        if (m.ws_rank.ensure((p.ws_bytes + 7) / 8) != hipSuccess)
+            return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of partial results)", p.ws_bytes);
+        const size_t n = (size_t)p.col_parts * (size_t)B;
+        a.ws_best = m.ws_rank.p;
+        a.ws_greater = reinterpret_cast<int32_t*>(m.ws_rank.p + n);
+        a.ws_tied = a.ws_greater + n;
+        a.ws_index = a.ws_tied + n;
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = launch(csp_rank_kernel_for(p.m_tiles, img_kind, p.has_head), dim3(p.grid), dim3(p.block), p.lds_bytes, s, a))
+        return rc;
+    if (p.col_parts == 1) return RANGE_OK;
+    return launch(csp_rank_merge_kernel, dim3(p.merge_grid), dim3(p.block), 0, s, a);
+}
+
+int range_csp_rank(range_ctx* c, const float* feats, int64_t B, const void* img, int32_t img_kind, const int32_t* labels,
+                   int32_t* greater, int32_t* tied_after, int32_t* argmax, range_stream_t stream) {
+    return range_csp_rank_grid(c, feats, B, img, img_kind, labels, greater, tied_after, argmax, 0, 0, stream);
+}
+
+int range_csp_predict_rank(range_ctx* c, const double* lonlat, int64_t B, const void* img, int32_t img_kind,
+                           const int32_t* labels, int32_t* greater, int32_t* tied_after, int32_t* argmax,
+                           range_stream_t stream) {
+    if (!c || !lonlat || !labels || !greater || !tied_after || !argmax) return fail(RANGE_ERR_INVALID, "null argument");
+    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (img_kind < 0 || img_kind >= CSP_IMG_KINDS) return fail(RANGE_ERR_INVALID, "img_kind %d", img_kind);
+    if ((img != nullptr) != (img_kind != CSP_IMG_NONE))
+        return fail(RANGE_ERR_INVALID, "img_kind %d %s image predictions", img_kind, img ? "with" : "without");
+    // the embeddings of a chunk of locations: range_csp_predict's chunks
+    const int64_t width = c->csp.plan.out_width, C = c->csp.num_classes;
+    const int64_t chunk = std::min<int64_t>(INT64_C(1) << 16, (INT64_C(1) << 24) / width / 64 * 64);
+    {
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+        if (c->csp.ws_feats.ensure((size_t)(std::min(B, chunk) * width)) != hipSuccess)
+            return fail(RANGE_ERR_NOMEM, "out of device memory (%lld bytes of embeddings)", (long long)(std::min(B, chunk) * width * 4));
+    }
+    const int64_t img_elem = img_kind == CSP_IMG_F64 ? 8 : 4;
+    for (int64_t i = 0; i < B; i += chunk) {
+        const int64_t n = std::min(chunk, B - i);
+        if (int rc = range_csp_encode_grid(c, lonlat + 2 * i, n, c->csp.ws_feats.p, 0, stream)) return rc;
+        const void* const img_i = img ? static_cast<const char*>(img) + i * C * img_elem : nullptr;
+        if (int rc = range_csp_rank_grid(c, c->csp.ws_feats.p, n, img_i, img_kind, labels + i, greater + i, tied_after + i,
+                                         argmax + i, 0, 0, stream))
+            return rc;
     }
     return RANGE_OK;
 }

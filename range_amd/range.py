@@ -380,6 +380,7 @@ class CspLocationModel(nn.Module):
         self.loc_enc = _CspLocEnc(p, engine.device)
         self.loc_emb_dim = p.num_filts
         self.num_classes = p.num_classes if p.class_emb is not None else 0
+        self.spa_enc_type = p.spa_enc_type
         self._engine = [engine]
         engine.set_csp(p.kind, p.freq_list, p.widths, p.weights, p.biases, p.ln_gamma, p.ln_beta,
                        CSP_ACTIVATIONS[p.activation], p.skip_connection, p.use_layn)
@@ -443,6 +444,49 @@ class CspLocationModel(nn.Module):
         sum is formed in the kernel (float32, a fixed order)."""
         self._need_head("class_sum")
         return self._engine[0].csp_predict(_as_coords(coords, self._engine[0].device), None, _native.CSP_HEAD_SUM)
+
+    #: label_ranks: bytes of image predictions on the GPU at a time
+    img_chunk_bytes = 256 << 20
+
+    @torch.no_grad()
+    def label_ranks(self, coords, labels, img_preds=None):
+        """What eval_helper.py's ``compute_acc_batch`` / ``get_label_rank`` make of ``self(coords, return_feats=False)``,
+        without the (B, num_classes) matrix (csp_rank_kernel.h): ``coords`` (B,2) (lon, lat) degrees, ``labels`` (B,)
+        integers, ``img_preds`` None or a numpy / torch array (B, num_classes), float32 or float64 (any other dtype is
+        refused, not cast) -> (``ranks``, ``pred_classes``), numpy int64 (B,) each: the rank, from 1, of the label
+        among the scores ``prior.double() * img_preds.double()`` (exact ties: the classes after the label count, as a
+        stable argsort reversed ranks them) and the arg-max.  Rows the reference drops - a NaN / infinite location,
+        a NaN score of the label - have rank 0 and class -1.  ValueError: a label outside ``[0, num_classes)``."""
+        self._need_head("label_ranks")
+        eng = self._engine[0]
+        x = _as_coords(coords, eng.device)
+        B, C = x.shape[0], self.num_classes
+        lab = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+        if lab.shape != (B,) or lab.dtype.kind not in "iu":
+            raise ValueError(f"labels: {B} integers, got {lab.dtype} {lab.shape}")
+        if B and (lab.min() < 0 or lab.max() >= C):
+            raise ValueError(f"labels outside 0 .. {C - 1}: min {lab.min()}, max {lab.max()}")
+        lab_dev = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32)).to(eng.device)
+        if img_preds is not None:
+            if not torch.is_tensor(img_preds):
+                img_preds = np.asarray(img_preds)
+                if img_preds.dtype not in (np.float32, np.float64):
+                    raise ValueError(f"img_preds must be float32 or float64, got {img_preds.dtype}")
+                img_preds = torch.from_numpy(img_preds)
+            if img_preds.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"img_preds must be float32 or float64, got {img_preds.dtype}")
+            if tuple(img_preds.shape) != (B, C):
+                raise ValueError(f"img_preds must be ({B}, {C}), got {tuple(img_preds.shape)}")
+        ranks, pred = np.zeros(B, dtype=np.int64), np.full(B, -1, dtype=np.int64)
+        step = B if img_preds is None else max(1, self.img_chunk_bytes // (C * img_preds.element_size()))
+        for i in range(0, B, max(step, 1)):
+            j = min(B, i + step)
+            img = None if img_preds is None else img_preds[i:j].to(eng.device).contiguous()
+            g, e, a = (t.cpu().numpy().astype(np.int64) for t in eng.csp_predict_rank(x[i:j], lab_dev[i:j], img))
+            keep = g >= 0
+            ranks[i:j][keep] = 1 + g[keep] + e[keep]
+            pred[i:j][keep] = a[keep]
+        return ranks, pred
 
 
 class _EncoderBase(nn.Module):
