@@ -75,4 +75,11 @@ struct DeviceGuard {
     }
 };
 
+// the context's device for the rest of the enclosing scope; a call that cannot have it is refused, not run elsewhere
+#define ENTER_DEVICE(c)                                       \
+    ::range_host::DeviceGuard device_guard__((c)->device);    \
+    if (!device_guard__.ok) return ::range_host::fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", (c)->device)
+
+inline bool aligned(const void* p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }   // (null is: optional arguments pass)
+
 }  // namespace range_host

@@ -755,6 +755,10 @@ inline void csp_pack_layer(const CspPlan& p, int i, const float* weight, const f
     }
 }
 
+// The composed calls (range_csp_predict, range_csp_predict_rank) encode a chunk of locations into a workspace and run
+// the head on it: rows of a chunk for embeddings `width` wide - at most 2^16, at most 64 MiB of float32, whole 64-row tiles.
+inline int64_t csp_predict_chunk(int width) { return std::min<int64_t>(INT64_C(1) << 16, (INT64_C(1) << 24) / width / 64 * 64); }
+
 // The CSP class head (csp_head_kernel.h; range_set_csp_head / range_csp_head): sigmoid(X W^T) of (B, num_filts)
 // embeddings and the (num_classes, num_filts) class_emb, bias-free - all classes, or the M classes an id array
 // names.  A workgroup of CSP_BLOCK threads holds a tile of 64 rows of X (32 when num_filts > 512: the LDS rule

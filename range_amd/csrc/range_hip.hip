@@ -490,8 +490,7 @@ int range_set_encoder(range_ctx* c, const range_encoder_desc* d, const double* c
     if (E != ENC_EMBED) return fail(RANGE_ERR_INVALID, "embed_dim %d unsupported (must be 256)", E);
     if (d->sh_mode != RANGE_SH_ANALYTIC && d->sh_mode != RANGE_SH_CLOSED_FORM)
         return fail(RANGE_ERR_INVALID, "unknown sh_mode %d", d->sh_mode);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
 
     // ---- slot plan, recurrence tables, weight packing: pure host arithmetic (host_plan.h, also
     //      built and run under sanitizers on the CPU: tests/native/host_sanitize.cpp)
@@ -548,8 +547,7 @@ int range_set_sh_table(range_ctx* c, int32_t L, const double* front, const doubl
     if (c->enc.desc.sh_mode != RANGE_SH_ANALYTIC)
         return fail(RANGE_ERR_INVALID, "the coefficient table belongs to the 'analytic' spherical harmonics");
     if (L != c->enc.desc.legendre_polys) return fail(RANGE_ERR_INVALID, "table for L=%d, encoder has L=%d", L, c->enc.desc.legendre_polys);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     std::vector<SHDesc> desc((size_t)L * L);
     for (int l = 0; l < L; ++l)
         for (int m = 0; m <= l; ++m) {
@@ -609,8 +607,7 @@ static int commit_bank(range_ctx* c, const float* keys, const float* values, con
                        int64_t n_rows, int64_t row_offset) {
     if (n_rows <= 0) return fail(RANGE_ERR_INVALID, "n_rows must be > 0");
     if (n_rows >= (int64_t)1 << 31) return fail(RANGE_ERR_INVALID, "n_rows too large");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     const int64_t n_pad = (n_rows + BLK - 1) / BLK * BLK;
     c->bank.has_bank = false;
     c->bank.has_values = false;
@@ -659,8 +656,7 @@ int range_set_keys(range_ctx* c, const float* keys, int64_t n_rows, int64_t row_
 int range_set_pv_mode(range_ctx* c, int32_t mode) {
     if (!c) return fail(RANGE_ERR_INVALID, "null argument");
     if (mode != RANGE_PV_EXACT && mode != RANGE_PV_BF16X3) return fail(RANGE_ERR_INVALID, "unknown pv mode %d", mode);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     c->bank.pv_mode = mode;
     if (mode == RANGE_PV_BF16X3 && c->bank.has_bank && c->bank.vplanes_groups == 0) return build_vplanes(c);
     return RANGE_OK;
@@ -726,8 +722,7 @@ __global__ void async_flag_kernel(const uint32_t* __restrict__ err, double* __re
 
 int range_async_error_flag(range_ctx* c, double* flag_dev, range_stream_t stream) {
     if (!c || !flag_dev) return fail(RANGE_ERR_INVALID, "null argument");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     if (!c->d_async_err) {            // (no host-mapped words in this context: nothing can have been reported)
         HIP_TRY(hipMemsetAsync(flag_dev, 0, sizeof(double), (hipStream_t)stream));
         return RANGE_OK;
@@ -741,8 +736,7 @@ static int encode_impl(range_ctx* c, const double* lonlat, int64_t B, double* eh
     if (!c->enc.has_encoder) return fail(RANGE_ERR_STATE, "encoder not set (range_set_encoder)");
     if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
     if (int rc = check_async_error(c)) return rc;
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     EncArgs a = c->enc.args;
     a.lonlat = lonlat;
     a.ehat64 = ehat64;
@@ -762,8 +756,7 @@ int range_encode(range_ctx* c, const double* lonlat, int64_t B, double* ehat64, 
 // queries, and the encoder into it; eraw64: the un-normalised outputs too, or null.
 static int encode_to_workspace(range_ctx* c, const double* lonlat, int64_t B, double* eraw64, range_stream_t stream) {
     if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     HIP_TRY(c->pass.ws_ehat64.ensure((size_t)B * 256));
     HIP_TRY(c->pass.ws_ehat32.ensure((size_t)B * 256));
     HIP_TRY(c->pass.ws_xq.ensure((size_t)B * 4));
@@ -816,7 +809,7 @@ int range_coord_features(range_ctx* c, int32_t mode, const double* lonlat, int64
     if (!c || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
     if (mode < 0 || mode > 2) return fail(RANGE_ERR_INVALID, "coordinate encoder mode %d", mode);
     if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    DeviceGuard g(c->device);
+    ENTER_DEVICE(c);
     return launch(coord_features_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, mode, lonlat, B, out);
 }
@@ -825,7 +818,7 @@ int range_blend(range_ctx* c, const float* G, const float* H, float beta, int64_
                 range_stream_t stream) {
     if (!c || !G || !H || !out) return fail(RANGE_ERR_INVALID, "null argument");
     if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    DeviceGuard g(c->device);
+    ENTER_DEVICE(c);
     const int64_t n4 = B * (VAL_DIM / 4);
     return launch(blend_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, G, H, beta, n4, out);
@@ -852,8 +845,7 @@ static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32,
         return fail(RANGE_ERR_INVALID, "queries [%lld, %lld) exceed the scan's %lld", (long long)first_query,
                     (long long)(first_query + B), (long long)total_queries);
     if (force_splits < 0) return fail(RANGE_ERR_INVALID, "n_splits must be >= 0");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     ScanArgs a{};
     hipStream_t s = (hipStream_t)stream;
     // a later chunk extends the scan only in order, and only when the first chunk could keep
@@ -1060,8 +1052,7 @@ static int topk_stream_impl(range_ctx* c, const float* ehat32, int64_t B, int32_
     if (!c->bank.has_bank) return fail(RANGE_ERR_STATE, "bank not set (range_set_bank)");
     if (B <= 0 || k <= 0 || k > MAX_TOPK) return fail(RANGE_ERR_INVALID, "bad B or k");
     if (int rc0 = check_async_error(c)) return rc0;
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     const TopkPlan p = plan_topk(c->n_cu, c->bank.n_rows, B, c->bank.key_norm_max, c->sw.topk_gemm, c->sw.topks_bf16,
                                  c->sw.topks_fused, c->sw.topks_force_exact, c->sw.tg_sample, PLAN_CONSTS);
@@ -1172,8 +1163,7 @@ int range_stream_read_timed(range_ctx* c, int32_t f32_keys, int32_t passes, int3
     if (!c || !avg_us) return fail(RANGE_ERR_INVALID, "null argument");
     if (!c->bank.has_bank) return fail(RANGE_ERR_STATE, "bank not set (range_set_bank)");
     if (passes < 1 || repeats < 2) return fail(RANGE_ERR_INVALID, "passes must be >= 1 and repeats >= 2");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_tiles = c->bank.n_pad / BLK;
     const u32x4* src = f32_keys ? reinterpret_cast<const u32x4*>(c->bank.d_keys.p) : reinterpret_cast<const u32x4*>(c->bank.d_keys_bf16.p);
@@ -1191,7 +1181,7 @@ int range_topk_stream_exact_count(range_ctx* c, int64_t* count) {
     if (!c || !count) return fail(RANGE_ERR_INVALID, "null argument");
     *count = 0;
     if (!c->topk.ws_exact_count.p) return RANGE_OK;
-    DeviceGuard g(c->device);
+    ENTER_DEVICE(c);
     int32_t v = 0;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(&v, c->topk.ws_exact_count.p, sizeof v, hipMemcpyDeviceToHost));
@@ -1203,8 +1193,7 @@ int range_merge_stats(range_ctx* c, const float* parts, int32_t n_parts, int64_t
                       range_stream_t stream) {
     if (!c || !parts || !out) return fail(RANGE_ERR_INVALID, "null argument");
     if (n_parts <= 0 || B <= 0) return fail(RANGE_ERR_INVALID, "n_parts and B must be > 0");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     const int tpb = 256;
     return launch(merge_stats_kernel, dim3((unsigned)((B + tpb - 1) / tpb)), dim3(tpb), 0,
                        (hipStream_t)stream, parts, n_parts, B, out);
@@ -1214,8 +1203,7 @@ int range_merge_topk(range_ctx* c, const float* val_parts, const int64_t* idx_pa
                      int64_t B, int32_t k, float* val_out, int64_t* idx_out, range_stream_t stream) {
     if (!c || !val_parts || !idx_parts || !val_out || !idx_out) return fail(RANGE_ERR_INVALID, "null argument");
     if (n_parts <= 0 || B <= 0 || k <= 0 || k > MAX_TOPK) return fail(RANGE_ERR_INVALID, "bad n_parts/B/k");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     return launch(merge_topk_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0,
                        (hipStream_t)stream, val_parts, (const int32_t*)nullptr, idx_parts, n_parts, B,
                        k, k, (int64_t)0, val_out, idx_out);
@@ -1241,8 +1229,7 @@ static int attend_impl(range_ctx* c, const float* ehat32, const float* xq32, int
                         (long long)(kept_first + B), (long long)c->kept.kept_B);
     }
     if (!diag_dev && !(beta >= 0.f && beta <= 1.f)) return fail(RANGE_ERR_INVALID, "beta must be in [0,1]");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     ScanArgs a{};
     int rc = fill_scan_args(c, a, ehat32, xq32, B, tau_sem, tau_geo);
     if (rc) return rc;
@@ -1329,8 +1316,7 @@ int range_stats_kept(range_ctx* c, int64_t first_query, const float* xq32, int64
     if (first_query + B > c->kept.kept_B)
         return fail(RANGE_ERR_INVALID, "queries [%lld, %lld) exceed the %lld kept", (long long)first_query,
                     (long long)(first_query + B), (long long)c->kept.kept_B);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     const KeptStatsPlan p = plan_kept_stats(c->n_cu, c->bank.n_rows, B, n_taus, n_splits, KEPT_MAX_PAIRS, PLAN_CONSTS);
     KeptStatsArgs a{};
@@ -1397,8 +1383,7 @@ int range_finalize(range_ctx* c, const float* partials, int32_t n_parts, const d
                    int64_t B, double* out, range_stream_t stream) {
     if (!c || !partials || !ehat64 || !out) return fail(RANGE_ERR_INVALID, "null argument");
     if (n_parts <= 0 || B <= 0) return fail(RANGE_ERR_INVALID, "n_parts and B must be > 0");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     const int64_t n = B * 320;
     return launch(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, partials, SlabMap{n_parts, 0, 0, 0, 1}, ehat64, B, (int64_t)0, B, out);
@@ -1481,7 +1466,7 @@ int range_forward(range_ctx* c, const double* lonlat, int64_t B, int32_t model, 
         // a handful of queries: one pass over the bank (attend_small.h)
         if (int lrc = encode_to_workspace(c, lonlat, B, nullptr, stream)) return lrc;
         c->pass.ws_queries = B;
-        DeviceGuard g(c->device);
+        ENTER_DEVICE(c);
         return forward_small(c, B, m, out, (hipStream_t)stream);
     }
     // single GPU: the finalize kernel sums the split slabs itself (same fixed order as
@@ -1489,7 +1474,7 @@ int range_forward(range_ctx* c, const double* lonlat, int64_t B, int32_t model, 
     SlabMap map{};
     if (int lrc = forward_to_slabs(c, lonlat, B, m, &map, stream)) return lrc;
     c->pass.ws_queries = B;
-    DeviceGuard g(c->device);
+    ENTER_DEVICE(c);
     const int64_t n = B * 320;
     return launch(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                   c->pass.ws_slabs.p, map, c->pass.ws_ehat64.p, B, (int64_t)0, B, out);
@@ -1512,8 +1497,7 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
     ModelParams m;
     if (int rc0 = model_params(c, model, beta, m)) return rc0;
     if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
+    ENTER_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     const size_t row_bytes = (size_t)RANGE_OUT_DIM * sizeof(double);
     HIP_TRY(c->host.ws_out64.ensure((size_t)B * RANGE_OUT_DIM));
@@ -1625,7 +1609,7 @@ int range_forward_host(range_ctx* c, const double* lonlat, int64_t B, int32_t mo
 
 int range_profile_enable(range_ctx* c, int32_t on) {
     if (!c) return fail(RANGE_ERR_INVALID, "null argument");
-    DeviceGuard g(c->device);
+    ENTER_DEVICE(c);
     for (auto& v : c->prof.pairs) {
         for (auto& p : v) { (void)hipEventSynchronize(p.second); c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
         v.clear();
@@ -1636,7 +1620,7 @@ int range_profile_enable(range_ctx* c, int32_t on) {
 
 int range_profile_read(range_ctx* c, int32_t which, double* total_ms, int32_t* launches) {
     if (!c || which < 0 || which >= RANGE_PROF_KINDS || !total_ms || !launches) return fail(RANGE_ERR_INVALID, "bad argument");
-    DeviceGuard g(c->device);
+    ENTER_DEVICE(c);
     double sum = 0.0;
     for (auto& p : c->prof.pairs[which]) {
         HIP_TRY(hipEventSynchronize(p.second));
@@ -1658,66 +1642,7 @@ int range_last_attend_geometry(const range_ctx* c, int32_t* n_query_tiles, int32
 
 }  // extern "C"
 
-// the positional encoders (posenc_kernel.h), by kind
-static void (*posenc_kernel_for(int kind))(PosencArgs) {
-    static void (*const posenc_kernels[PE_KINDS])(PosencArgs) = {
-        posenc_features_kernel<PE_THEORY>, posenc_features_kernel<PE_GRID>, posenc_features_kernel<PE_SPHEREC>,
-        posenc_features_kernel<PE_SPHERECPLUS>, posenc_features_kernel<PE_SPHEREM>, posenc_features_kernel<PE_SPHEREMPLUS>};
-    return posenc_kernels[kind];
-}
-
-// The device copy of a frequency table: the context keeps every table it has seen (a model has one; at
-// most POSENC_TABLES_MAX, beyond which the device is drained and the tables are dropped).  A new table
-// costs one allocation and a synchronous upload; a known one nothing.
-constexpr size_t POSENC_TABLES_MAX = 64;
-static int posenc_table(range_ctx* c, const double* freq_host, int32_t F, const double** dev) {
-    auto& tables = c->posenc.tables;
-    for (auto& t : tables)
-        if ((int32_t)t->host.size() == F && std::memcmp(t->host.data(), freq_host, (size_t)F * sizeof(double)) == 0) {
-            *dev = t->dev.p;
-            return RANGE_OK;
-        }
-    if (tables.size() >= POSENC_TABLES_MAX) {
-        HIP_TRY(hipDeviceSynchronize());
-        tables.clear();
-    }
-    auto t = std::make_unique<range_ctx::Posenc::Table>();
-    t->host.assign(freq_host, freq_host + F);
-    HIP_TRY(t->dev.upload(t->host));
-    *dev = t->dev.p;
-    tables.push_back(std::move(t));
-    return RANGE_OK;
-}
-
-extern "C" {
-
-int32_t range_posenc_width(int32_t kind, int32_t F) {
-    if (F < 1 || F > POSENC_MAX_F) return 0;
-    return posenc_per_freq(kind) * F;
-}
-
-int range_posenc_features(range_ctx* c, int32_t kind, const double* freq_host, int32_t F, const double* lonlat,
-                          int64_t B, double* out, range_stream_t stream) {
-    if (!c || !freq_host || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
-    if (kind < 0 || kind >= PE_KINDS) return fail(RANGE_ERR_INVALID, "positional encoder kind %d", kind);
-    if (F < 1 || F > POSENC_MAX_F) return fail(RANGE_ERR_INVALID, "F = %d frequencies (1 .. %d)", F, POSENC_MAX_F);
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(RANGE_ERR_INVALID, "out_dev must be 16-byte aligned");
-    const PosencPlan p = posenc_plan(kind, F, B);
-    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld locations: output too large", (long long)B);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    PosencArgs a{};
-    if (int rc = posenc_table(c, freq_host, F, &a.freq)) return rc;
-    a.lonlat = lonlat;
-    a.out = out;
-    a.B = B;
-    a.n_tiles = p.n_tiles;
-    a.F = F;
-    return launch(posenc_kernel_for(kind), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
-}
-
-}  // extern "C"
+#include "posenc_host.h"   // (the side encoders' host code, each with its kernel tables: in this order, around the two below)
 
 static void (*sharp_scan_kernel(bool geo))(ScanArgs) {
     // [0: with the geographic head, 1: without]
@@ -1735,347 +1660,5 @@ static void (*kept_stats_kernel_for(int n_pairs, bool geo))(KeptStatsArgs) {
     return kept_kernels[n_pairs - 1][!geo];
 }
 
-// ---- the CSP location encoders (csp_kernel.h), by tile height (32 m_tiles rows) and activation
-static void (*csp_kernel_for(int m_tiles, int act))(CspArgs) {
-    static void (*const csp_kernels[2][CSP_ACTS])(CspArgs) = {
-        {csp_encode_kernel<1, 0>, csp_encode_kernel<1, 1>, csp_encode_kernel<1, 2>, csp_encode_kernel<1, 3>, csp_encode_kernel<1, 4>},
-        {csp_encode_kernel<2, 0>, csp_encode_kernel<2, 1>, csp_encode_kernel<2, 2>, csp_encode_kernel<2, 3>, csp_encode_kernel<2, 4>}};
-    return csp_kernels[m_tiles - 1][act];
-}
-
-// ---- the CSP class head (csp_head_kernel.h), by tile height and output
-static void (*csp_head_kernel_for(int m_tiles, int mode))(CspHeadArgs) {
-    static void (*const csp_head_kernels[2][CSP_HEAD_MODES])(CspHeadArgs) = {
-        {csp_head_kernel<1, 0>, csp_head_kernel<1, 1>, csp_head_kernel<1, 2>},
-        {csp_head_kernel<2, 0>, csp_head_kernel<2, 1>, csp_head_kernel<2, 2>}};
-    return csp_head_kernels[m_tiles - 1][mode];
-}
-
-// ---- the evaluation behind the head (csp_rank_kernel.h), by tile height, image predictions and embeddings
-static void (*csp_rank_kernel_for(int m_tiles, int img_kind, bool has_head))(CspRankArgs) {
-    static void (*const with_head[2][CSP_IMG_KINDS])(CspRankArgs) = {
-        {csp_rank_kernel<1, 0, true>, csp_rank_kernel<1, 1, true>, csp_rank_kernel<1, 2, true>},
-        {csp_rank_kernel<2, 0, true>, csp_rank_kernel<2, 1, true>, csp_rank_kernel<2, 2, true>}};
-    static void (*const without[CSP_IMG_KINDS])(CspRankArgs) = {nullptr, csp_rank_kernel<2, 1, false>,
-                                                                csp_rank_kernel<2, 2, false>};
-    return has_head ? with_head[m_tiles - 1][img_kind] : without[img_kind];
-}
-
-extern "C" {
-
-int range_set_csp(range_ctx* c, int32_t kind, const double* freq_host, int32_t F, int32_t n_layers, const int32_t* widths,
-                  const float* const* weights, const float* const* biases, const float* const* ln_gamma,
-                  const float* const* ln_beta, int32_t act, int32_t skip, int32_t use_layn) {
-    if (!c || !freq_host || !widths || !weights || !biases) return fail(RANGE_ERR_INVALID, "null argument");
-    if (act < 0 || act >= CSP_ACTS) return fail(RANGE_ERR_INVALID, "activation %d", act);
-    if (n_layers < 1 || n_layers > CSP_MAX_LAYERS)
-        return fail(RANGE_ERR_INVALID, "%d linear layers (1 .. %d: at most 8 hidden layers)", n_layers, CSP_MAX_LAYERS);
-    int w[CSP_MAX_LAYERS];
-    for (int i = 0; i < n_layers; ++i) w[i] = widths[i];
-    const CspPlan p = csp_plan(kind, F, n_layers, w, skip != 0, use_layn != 0, 1);
-    if (!p.valid) return fail(RANGE_ERR_INVALID, "CSP network outside the supported envelope: %s", p.why);
-    for (int i = 0; i < n_layers; ++i) {
-        if (!weights[i] || !biases[i]) return fail(RANGE_ERR_INVALID, "null parameters of layer %d", i);
-        if (p.layer[i].layn && (!ln_gamma || !ln_beta || !ln_gamma[i] || !ln_beta[i]))
-            return fail(RANGE_ERR_INVALID, "null LayerNorm parameters of layer %d", i);
-    }
-    std::vector<float> packed(p.packed_floats, 0.0f);
-    for (int i = 0; i < n_layers; ++i)
-        csp_pack_layer(p, i, weights[i], biases[i], p.layer[i].layn ? ln_gamma[i] : nullptr,
-                       p.layer[i].layn ? ln_beta[i] : nullptr, packed.data());
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    // a launch in flight on any stream may still read the parameters this call replaces
-    HIP_TRY(hipDeviceSynchronize());
-    c->csp.has = false;
-    c->csp.num_classes = 0;          // a head belongs to the network it was installed behind
-    HIP_TRY(c->csp.d_params.upload(packed));
-    HIP_TRY(c->csp.d_freq.upload(std::vector<double>(freq_host, freq_host + F)));
-    std::vector<CspLayerArgs> layers;
-    for (int i = 0; i < n_layers; ++i) {
-        const CspLayerPlan& l = p.layer[i];
-        layers.push_back(CspLayerArgs{l.out, l.n_tiles, l.k_groups, l.skip, l.layn, (uint32_t)l.w_off, (uint32_t)l.b_off,
-                                      (uint32_t)l.g_off, (uint32_t)l.be_off});
-    }
-    HIP_TRY(c->csp.d_layers.upload(layers));
-    c->csp.kind = kind;
-    c->csp.F = F;
-    c->csp.act = act;
-    c->csp.skip = skip != 0;
-    c->csp.layn = use_layn != 0;
-    std::copy(w, w + n_layers, c->csp.widths);
-    c->csp.plan = p;
-    c->csp.has = true;
-    return RANGE_OK;
-}
-
-int32_t range_csp_width(const range_ctx* c) { return c && c->csp.has ? c->csp.plan.out_width : 0; }
-
-int32_t range_csp_tile_rows(const range_ctx* c) { return c && c->csp.has ? c->csp.plan.tile_rows : 0; }
-
-int range_csp_encode_grid(range_ctx* c, const double* lonlat, int64_t B, float* out, int64_t max_grid,
-                          range_stream_t stream) {
-    if (!c || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
-    if (!c->csp.has) return fail(RANGE_ERR_INVALID, "no CSP network set (range_set_csp)");
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (max_grid < 0) return fail(RANGE_ERR_INVALID, "max_grid must be >= 0");
-    if (reinterpret_cast<uintptr_t>(lonlat) % 8 || reinterpret_cast<uintptr_t>(out) % 4)
-        return fail(RANGE_ERR_INVALID, "lonlat_dev must be 8-byte aligned, out_dev 4-byte aligned");
-    const range_ctx::Csp& m = c->csp;
-    const CspPlan p = csp_plan(m.kind, m.F, m.plan.n_layers, m.widths, m.skip, m.layn, B, max_grid);
-    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld locations: %s", (long long)B, p.why);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    CspArgs a{};
-    a.freq = m.d_freq.p;
-    a.lonlat = lonlat;
-    a.params = m.d_params.p;
-    a.out = out;
-    a.B = B;
-    a.n_tiles = p.n_tiles;
-    a.F = m.F;
-    a.kind = m.kind;
-    a.layer = m.d_layers.p;
-    a.n_layers = p.n_layers;
-    a.ld = p.ld;
-    a.in0 = p.in0;
-    a.in0_pad = p.layer[0].k_pad();
-    return launch(csp_kernel_for(p.m_tiles, m.act), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
-}
-
-int range_set_csp_head(range_ctx* c, const float* class_emb, int32_t C) {
-    if (!c || !class_emb) return fail(RANGE_ERR_INVALID, "null argument");
-    if (!c->csp.has) return fail(RANGE_ERR_INVALID, "no CSP network set (range_set_csp): the head needs its num_filts");
-    const CspHeadPlan p = csp_head_plan(c->csp.plan.out_width, C, C, 1, CSP_HEAD_PROBS);
-    if (!p.valid) return fail(RANGE_ERR_INVALID, "CSP class head outside the supported envelope: %s", p.why);
-    std::vector<float> packed(p.packed_floats, 0.0f);
-    csp_pack_head(p, class_emb, packed.data());
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    HIP_TRY(hipDeviceSynchronize());         // a launch in flight may still read the head this call replaces
-    c->csp.num_classes = 0;
-    HIP_TRY(c->csp.d_head.upload(packed));
-    c->csp.num_classes = C;
-    return RANGE_OK;
-}
-
-int32_t range_csp_classes(const range_ctx* c) { return c && c->csp.has ? c->csp.num_classes : 0; }
-
-int32_t range_csp_head_cols_per_pass(const range_ctx* c) {
-    if (!c || !c->csp.has || !c->csp.num_classes) return 0;
-    return csp_head_plan(c->csp.plan.out_width, c->csp.num_classes, c->csp.num_classes, 1, CSP_HEAD_PROBS).cols_per_pass;
-}
-
-int range_csp_check_ids(range_ctx* c, const int32_t* ids_host, int32_t M) {
-    if (!c || !ids_host) return fail(RANGE_ERR_INVALID, "null argument");
-    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
-    if (M < 1) return fail(RANGE_ERR_INVALID, "M must be > 0");
-    for (int32_t i = 0; i < M; ++i)
-        if (ids_host[i] < 0 || ids_host[i] >= c->csp.num_classes)
-            return fail(RANGE_ERR_INVALID, "class id %d (entry %d) outside 0 .. %d", ids_host[i], i, c->csp.num_classes - 1);
-    return RANGE_OK;
-}
-
-int range_csp_head_grid(range_ctx* c, const float* feats, int64_t B, const int32_t* ids, int32_t M, int32_t mode,
-                        float* out, int64_t max_grid, range_stream_t stream) {
-    if (!c || !feats || !out) return fail(RANGE_ERR_INVALID, "null argument");
-    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (M < 1) return fail(RANGE_ERR_INVALID, "M must be > 0");
-    if (max_grid < 0) return fail(RANGE_ERR_INVALID, "max_grid must be >= 0");
-    if (mode < 0 || mode >= CSP_HEAD_MODES) return fail(RANGE_ERR_INVALID, "mode %d", mode);
-    if (mode == CSP_HEAD_SUM && ids) return fail(RANGE_ERR_INVALID, "SUM runs over all classes: no class ids");
-    if (!ids && M != c->csp.num_classes)
-        return fail(RANGE_ERR_INVALID, "M = %d without class ids: the head has %d classes", M, c->csp.num_classes);
-    if (reinterpret_cast<uintptr_t>(feats) % 4 || reinterpret_cast<uintptr_t>(out) % 4 || reinterpret_cast<uintptr_t>(ids) % 4)
-        return fail(RANGE_ERR_INVALID, "the device pointers must be 4-byte aligned");
-    const range_ctx::Csp& m = c->csp;
-    const CspHeadPlan p = csp_head_plan(m.plan.out_width, m.num_classes, M, B, mode, max_grid);
-    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld, M = %d: %s", (long long)B, M, p.why);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    CspHeadArgs a{};
-    a.x = feats;
-    a.w4 = reinterpret_cast<const float4*>(m.d_head.p);
-    a.ids = ids;
-    a.out = out;
-    a.B = B;
-    a.n_items = p.n_items;
-    a.K = p.num_filts;
-    a.k_groups = p.k_groups;
-    a.ld = p.ld;
-    a.M = p.M;
-    a.col_tiles = p.col_tiles;
-    a.n_chunks = p.n_chunks;
-    a.num_classes = p.num_classes;
-    a.chunks_per_item = p.chunks_per_item;
-    a.groups = p.groups;
-    return launch(csp_head_kernel_for(p.m_tiles, mode), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
-}
-
-int range_csp_head(range_ctx* c, const float* feats, int64_t B, const int32_t* ids, int32_t M, int32_t mode, float* out,
-                   range_stream_t stream) {
-    return range_csp_head_grid(c, feats, B, ids, M, mode, out, 0, stream);
-}
-
-int range_csp_predict(range_ctx* c, const double* lonlat, int64_t B, const int32_t* ids, int32_t M, int32_t mode,
-                      float* out, range_stream_t stream) {
-    if (!c || !lonlat || !out) return fail(RANGE_ERR_INVALID, "null argument");
-    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (M < 1) return fail(RANGE_ERR_INVALID, "M must be > 0");
-    if (mode < 0 || mode >= CSP_HEAD_MODES) return fail(RANGE_ERR_INVALID, "mode %d", mode);
-    // the embeddings of a chunk of locations: at most 64 MiB, whole 64-row tiles
-    const int64_t width = c->csp.plan.out_width;
-    const int64_t chunk = std::min<int64_t>(INT64_C(1) << 16, (INT64_C(1) << 24) / width / 64 * 64);
-    {
-        DeviceGuard g(c->device);
-        if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-        if (c->csp.ws_feats.ensure((size_t)(std::min(B, chunk) * width)) != hipSuccess)
-            return fail(RANGE_ERR_NOMEM, "out of device memory (%lld bytes of embeddings)", (long long)(std::min(B, chunk) * width * 4));
-    }
-    const int64_t out_stride = mode == CSP_HEAD_SUM ? 1 : M;
-    for (int64_t i = 0; i < B; i += chunk) {
-        const int64_t n = std::min(chunk, B - i);
-        if (int rc = range_csp_encode_grid(c, lonlat + 2 * i, n, c->csp.ws_feats.p, 0, stream)) return rc;
-        if (int rc = range_csp_head_grid(c, c->csp.ws_feats.p, n, ids, M, mode, out + i * out_stride, 0, stream)) return rc;
-    }
-    return RANGE_OK;
-}
-
-int range_csp_rank_grid(range_ctx* c, const float* feats, int64_t B, const void* img, int32_t img_kind, const int32_t* labels,
-                        int32_t* greater, int32_t* tied_after, int32_t* argmax, int64_t max_grid, int32_t col_parts,
-                        range_stream_t stream) {
-    if (!c || !labels || !greater || !tied_after || !argmax) return fail(RANGE_ERR_INVALID, "null argument");
-    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
-    if (!feats && !img) return fail(RANGE_ERR_INVALID, "neither embeddings nor image predictions");
-    if (img_kind < 0 || img_kind >= CSP_IMG_KINDS) return fail(RANGE_ERR_INVALID, "img_kind %d", img_kind);
-    if ((img != nullptr) != (img_kind != CSP_IMG_NONE))
-        return fail(RANGE_ERR_INVALID, "img_kind %d %s image predictions", img_kind, img ? "with" : "without");
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (max_grid < 0 || col_parts < 0) return fail(RANGE_ERR_INVALID, "max_grid and col_parts must be >= 0");
-    if (reinterpret_cast<uintptr_t>(feats) % 4 || reinterpret_cast<uintptr_t>(labels) % 4 ||
-        reinterpret_cast<uintptr_t>(greater) % 4 || reinterpret_cast<uintptr_t>(tied_after) % 4 ||
-        reinterpret_cast<uintptr_t>(argmax) % 4 || reinterpret_cast<uintptr_t>(img) % (img_kind == CSP_IMG_F64 ? 8 : 4))
-        return fail(RANGE_ERR_INVALID, "the device pointers must be aligned to their element");
-    range_ctx::Csp& m = c->csp;
-    const CspRankPlan p = csp_rank_plan(m.plan.out_width, m.num_classes, B, img_kind, feats != nullptr, max_grid, col_parts);
-    if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld, col_parts = %d: %s", (long long)B, col_parts, p.why);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    CspRankArgs a{};
-    a.x = feats;
-    a.w4 = reinterpret_cast<const float4*>(m.d_head.p);
-    a.img = img;
-    a.labels = labels;
-    a.greater = greater;
-    a.tied = tied_after;
-    a.argmax = argmax;
-    a.B = B;
-    a.n_items = p.n_items;
-    a.K = p.num_filts;
-    a.k_groups = p.k_groups;
-    a.ld = p.ld;
-    a.C = p.num_classes;
-    a.col_tiles = p.col_tiles;
-    a.n_chunks = p.n_chunks;
-    a.col_parts = p.col_parts;
-    if (p.col_parts > 1) {
-        if (m.ws_rank.ensure((p.ws_bytes + 7) / 8) != hipSuccess)
-            return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of partial results)", p.ws_bytes);
-        const size_t n = (size_t)p.col_parts * (size_t)B;
-        a.ws_best = m.ws_rank.p;
-        a.ws_greater = reinterpret_cast<int32_t*>(m.ws_rank.p + n);
-        a.ws_tied = a.ws_greater + n;
-        a.ws_index = a.ws_tied + n;
-    }
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = launch(csp_rank_kernel_for(p.m_tiles, img_kind, p.has_head), dim3(p.grid), dim3(p.block), p.lds_bytes, s, a))
-        return rc;
-    if (p.col_parts == 1) return RANGE_OK;
-    return launch(csp_rank_merge_kernel, dim3(p.merge_grid), dim3(p.block), 0, s, a);
-}
-
-int range_csp_rank(range_ctx* c, const float* feats, int64_t B, const void* img, int32_t img_kind, const int32_t* labels,
-                   int32_t* greater, int32_t* tied_after, int32_t* argmax, range_stream_t stream) {
-    return range_csp_rank_grid(c, feats, B, img, img_kind, labels, greater, tied_after, argmax, 0, 0, stream);
-}
-
-int range_csp_predict_rank(range_ctx* c, const double* lonlat, int64_t B, const void* img, int32_t img_kind,
-                           const int32_t* labels, int32_t* greater, int32_t* tied_after, int32_t* argmax,
-                           range_stream_t stream) {
-    if (!c || !lonlat || !labels || !greater || !tied_after || !argmax) return fail(RANGE_ERR_INVALID, "null argument");
-    if (!c->csp.has || !c->csp.num_classes) return fail(RANGE_ERR_INVALID, "no CSP class head set (range_set_csp_head)");
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (img_kind < 0 || img_kind >= CSP_IMG_KINDS) return fail(RANGE_ERR_INVALID, "img_kind %d", img_kind);
-    if ((img != nullptr) != (img_kind != CSP_IMG_NONE))
-        return fail(RANGE_ERR_INVALID, "img_kind %d %s image predictions", img_kind, img ? "with" : "without");
-    // the embeddings of a chunk of locations: range_csp_predict's chunks
-    const int64_t width = c->csp.plan.out_width, C = c->csp.num_classes;
-    const int64_t chunk = std::min<int64_t>(INT64_C(1) << 16, (INT64_C(1) << 24) / width / 64 * 64);
-    {
-        DeviceGuard g(c->device);
-        if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-        if (c->csp.ws_feats.ensure((size_t)(std::min(B, chunk) * width)) != hipSuccess)
-            return fail(RANGE_ERR_NOMEM, "out of device memory (%lld bytes of embeddings)", (long long)(std::min(B, chunk) * width * 4));
-    }
-    const int64_t img_elem = img_kind == CSP_IMG_F64 ? 8 : 4;
-    for (int64_t i = 0; i < B; i += chunk) {
-        const int64_t n = std::min(chunk, B - i);
-        if (int rc = range_csp_encode_grid(c, lonlat + 2 * i, n, c->csp.ws_feats.p, 0, stream)) return rc;
-        const void* const img_i = img ? static_cast<const char*>(img) + i * C * img_elem : nullptr;
-        if (int rc = range_csp_rank_grid(c, c->csp.ws_feats.p, n, img_i, img_kind, labels + i, greater + i, tied_after + i,
-                                         argmax + i, 0, 0, stream))
-            return rc;
-    }
-    return RANGE_OK;
-}
-
-int range_csp_encode(range_ctx* c, const double* lonlat, int64_t B, float* out, range_stream_t stream) {
-    return range_csp_encode_grid(c, lonlat, B, out, 0, stream);
-}
-
-}  // extern "C"
-
-// ---- the checkerboard task's nearest-support scan (checker_kernel.h)
-extern "C" {
-
-int range_nearest_support(range_ctx* c, const double* q, int64_t Q, const double* sup, int64_t S, int32_t exclude_self,
-                          int32_t max_chunks, int64_t* idx, double* dist, range_stream_t stream) {
-    if (!c || !q || !sup || !idx) return fail(RANGE_ERR_INVALID, "null argument");
-    if (Q < 1 || S < 1) return fail(RANGE_ERR_INVALID, "Q and S must be > 0");
-    if (max_chunks < 0) return fail(RANGE_ERR_INVALID, "max_chunks must be >= 0");
-    if (exclude_self && (Q != S || S < 2))
-        return fail(RANGE_ERR_INVALID, "exclude_self needs the same Q = S >= 2 points on both sides (Q = %lld, S = %lld)",
-                    (long long)Q, (long long)S);
-    if (reinterpret_cast<uintptr_t>(q) % 8 || reinterpret_cast<uintptr_t>(sup) % 8 || reinterpret_cast<uintptr_t>(idx) % 8 ||
-        reinterpret_cast<uintptr_t>(dist) % 8)
-        return fail(RANGE_ERR_INVALID, "the device pointers must be 8-byte aligned");
-    const CheckerPlan p = checker_plan(Q, S, exclude_self != 0, max_chunks);
-    if (!p.valid) return fail(RANGE_ERR_INVALID, "Q = %lld, S = %lld: too many points", (long long)Q, (long long)S);
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail(RANGE_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    const hipStream_t s = (hipStream_t)stream;
-    CheckerArgs a{};
-    a.q = q;
-    a.s = sup;
-    a.Q = Q;
-    a.S = S;
-    a.q_blocks = p.q_blocks;
-    a.s_tiles = p.s_tiles;
-    a.exclude_self = exclude_self != 0;
-    a.idx = idx;
-    a.dist = dist;
-    if (p.chunks > 1) {
-        if (c->checker.ws_a.ensure(p.ws_pairs) != hipSuccess || c->checker.ws_idx.ensure(p.ws_pairs) != hipSuccess)
-            return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of partial results)", p.ws_bytes);
-        a.part_a = c->checker.ws_a.p;
-        a.part_idx = c->checker.ws_idx.p;
-    }
-    if (int rc = launch(checker_scan_kernel, dim3(p.grid_x, (unsigned)p.chunks), dim3(p.block), p.lds_bytes, s, a)) return rc;
-    if (p.chunks == 1) return RANGE_OK;
-    return launch(checker_merge_kernel, dim3(p.merge_grid), dim3(p.block), 0, s, (const double*)a.part_a,
-                  (const int64_t*)a.part_idx, (int32_t)p.chunks, Q, idx, dist);
-}
-
-}  // extern "C"
+#include "csp_host.h"
+#include "checker_host.h"

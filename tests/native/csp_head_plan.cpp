@@ -3,7 +3,8 @@
 // tests/test_csp_head_cpu.py.  At the corners of the envelope: every class_emb (n, k) lands exactly once in the
 // packed image, where the kernel's lane reads it (csp_head_kernel.h), the padding is zero; every index the kernel
 // forms stays inside the LDS image and the packed image; the work items of a launch - walked grid-stride by
-// the workgroups, every wave its column tiles - cover B x M exactly once, also with a capped grid; the refusals.
+// the workgroups, every wave its column tiles - cover B x M exactly once, also with a capped grid; the refusals;
+// the rows of a chunk of the composed calls (csp_predict_chunk) at every width.
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
@@ -136,6 +137,13 @@ int main() {
     CHECK(!csp_head_plan(256, 5, 5, 1, 0, -1).valid);
     CHECK(!csp_head_plan(256, 5, 3, 1, CSP_HEAD_SUM).valid && csp_head_plan(256, 5, 5, 1, CSP_HEAD_SUM).valid);
     CHECK(*csp_head_plan(256, 32769, 1, 1, 0).why != 0);
+    // a chunk of the composed calls: whole 64-row tiles, at most 2^16 rows and 64 MiB of float32 embeddings
+    for (int width = 1; width <= CSP_MAX_WIDTH; ++width) {
+        const int64_t chunk = csp_predict_chunk(width);
+        CHECK(chunk > 0 && chunk % 64 == 0 && chunk <= 65536 && chunk * width * 4 <= (INT64_C(64) << 20));
+        CHECK(chunk == std::min<int64_t>(INT64_C(1) << 16, (INT64_C(1) << 24) / width / 64 * 64));
+    }
+    for (int width : {256, 257, 1024}) std::printf("csp_predict_chunk(%d) = %lld\n", width, (long long)csp_predict_chunk(width));
     std::printf("csp_head_plan ok\n");
     return 0;
 }

@@ -137,8 +137,8 @@ def test_class_head_option_is_for_csp(tmp_path):
 
 
 def test_csp_head_plan_under_sanitizers(tmp_path):
-    """host_plan.h: csp_head_plan / csp_pack_head (tests/native/csp_head_plan.cpp) compiled with g++ under
-    AddressSanitizer and UndefinedBehaviorSanitizer and run on the CPU."""
+    """host_plan.h: csp_head_plan / csp_pack_head / csp_predict_chunk (tests/native/csp_head_plan.cpp) compiled with
+    g++ under AddressSanitizer and UndefinedBehaviorSanitizer and run on the CPU."""
     exe = str(tmp_path / "csp_head_plan")
     src = os.path.join(REPO, "tests", "native", "csp_head_plan.cpp")
     subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
@@ -146,6 +146,8 @@ def test_csp_head_plan_under_sanitizers(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
     p = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0 and "csp_head_plan ok" in p.stdout, p.stdout + p.stderr
+    for width, chunk in ((256, 65536), (257, 65280), (1024, 16384)):
+        assert f"csp_predict_chunk({width}) = {chunk}\n" in p.stdout, p.stdout
 
 
 def float32_limits(head, kind):
