@@ -979,4 +979,61 @@ inline CheckerPlan checker_plan(int64_t Q, int64_t S, bool exclude_self, int max
     return p;
 }
 
+// The embedding map (map_kernels.h; include/range_map.h).  Three row walks over n rows:
+//   * projection: a workgroup of MAP_BLOCK threads takes MAP_PROJ_ROWS rows a trip (MAP_PROJ_WAVE_ROWS per
+//     wave), the grid is capped at MAP_MAX_GRID workgroups and walks the row groups grid-stride;
+//   * ICA step: the rows are cut into slabs of `chunk` = MAP_BLOCK * ipt rows, a cut that depends on n alone
+//     (never on the grid): every slab's partial sums are formed in one fixed order and stored apart, and a fold
+//     adds the slabs in index order.  The grid only decides which workgroup computes which slab, so a capped
+//     grid (max_grid) gives the same bits.  ipt grows with n so that there are never more than MAP_MAX_SLABS;
+//   * equalisation (histogram and interpolation): MAP_BLOCK rows a trip, grid capped at MAP_MAX_GRID.
+// The workspace holds the slabs: slabs * (c*c + c) doubles.
+constexpr int MAP_BLOCK = 256;
+constexpr int MAP_MAX_C = 8;
+constexpr int MAP_MAX_BINS = 1024;
+constexpr int MAP_PROJ_WAVE_ROWS = 8;
+constexpr int MAP_PROJ_ROWS = MAP_PROJ_WAVE_ROWS * (MAP_BLOCK / 64);
+constexpr int MAP_MIN_IPT = 4;
+constexpr int64_t MAP_MAX_SLABS = 2048;
+constexpr int64_t MAP_MAX_GRID = 2048;            // 256 CUs x 8 workgroups of 4 waves
+constexpr int64_t MAP_MAX_ROWS = INT64_C(1) << 40;
+
+struct MapPlan {
+    bool valid = false;
+    int block = MAP_BLOCK;
+    int64_t proj_groups = 0;            // row groups of the projection
+    unsigned proj_grid = 0;
+    int64_t ipt = 0, chunk = 0;         // ICA step: rows per thread and per slab
+    int64_t slabs = 0;
+    unsigned step_grid = 0;
+    int slab_doubles = 0;               // c*c + c
+    size_t ws_bytes = 0;
+    int64_t eq_blocks = 0;
+    unsigned eq_grid = 0;
+    // slabs workgroup x computes (x, x + step_grid, ...); rows of slab s
+    int64_t slabs_of(int64_t x) const { return x < slabs ? (slabs - x + step_grid - 1) / step_grid : 0; }
+    int64_t slab_rows(int64_t s, int64_t n) const { return s < slabs ? std::min(chunk, n - s * chunk) : 0; }
+};
+
+// max_grid: 0 the plan's choice, g > 0 at most g workgroups a launch (tests of the second trip).
+// Invalid: n < 1 or beyond 2^40, c outside 1..MAP_MAX_C, a negative max_grid.
+inline MapPlan map_plan(int64_t n, int c, int64_t max_grid = 0) {
+    MapPlan p;
+    if (n < 1 || n > MAP_MAX_ROWS || c < 1 || c > MAP_MAX_C || max_grid < 0) return p;
+    const int64_t cap = max_grid > 0 ? std::min(max_grid, MAP_MAX_GRID) : MAP_MAX_GRID;
+    p.proj_groups = (n + MAP_PROJ_ROWS - 1) / MAP_PROJ_ROWS;
+    p.proj_grid = (unsigned)std::min(p.proj_groups, cap);
+    const int64_t per_slab = (n + MAP_MAX_SLABS - 1) / MAP_MAX_SLABS;
+    p.ipt = std::max<int64_t>(MAP_MIN_IPT, (per_slab + MAP_BLOCK - 1) / MAP_BLOCK);
+    p.chunk = p.ipt * MAP_BLOCK;
+    p.slabs = (n + p.chunk - 1) / p.chunk;
+    p.step_grid = (unsigned)std::min(p.slabs, cap);
+    p.slab_doubles = c * c + c;
+    p.ws_bytes = (size_t)p.slabs * (size_t)p.slab_doubles * sizeof(double);
+    p.eq_blocks = (n + MAP_BLOCK - 1) / MAP_BLOCK;
+    p.eq_grid = (unsigned)std::min(p.eq_blocks, cap);
+    p.valid = true;
+    return p;
+}
+
 }  // namespace range_host

@@ -17,6 +17,7 @@ struct range_probe_ctx {
     int device = 0;
     int n_cu = 256;
     DevBuf<double> ws_slabs, ws_part, ws_A, d_ntr, d_alphas;
+    DevBuf<double> ws_map;   // the ICA step's slabs (map_host.h), sized by range_map_reserve
     DevBuf<int32_t> d_info;
 };
 
@@ -346,3 +347,6 @@ int range_probe_accuracy(range_probe_ctx* c, const double* P, const double* c0, 
 }
 
 }  // extern "C"
+
+// the embedding map's entry points (include/range_map.h)
+#include "map_host.h"
