@@ -14,7 +14,9 @@ NaN if there is one.  A row whose label's score is NaN has no rank: 0 here, pred
 
 numpy only: importable, and testable, without a GPU.  ``compute_acc_batch`` with a CSP prior runs
 ``CspLocationModel.label_ranks`` - one kernel launch per chunk, three integers per sample, no (B, num_classes)
-matrix."""
+matrix.  The location-only baselines ``'train_freq'``, ``'nn_dist'``, ``'nn_knn'`` and ``'grid'`` take the
+objects of ``range_amd.geo_baselines`` as ``prior`` (a (C,) array for ``'train_freq'``); as in the reference they
+keep every row - a NaN location has the uniform prior."""
 from __future__ import annotations
 
 import logging
@@ -24,7 +26,10 @@ import numpy as np
 
 TOP_KS = (1, 3, 5, 10)
 #: prior types of eval_helper.py this module does not serve
-UNSUPPORTED_PRIORS = ("train_freq", "nn_dist", "nn_knn", "kde", "grid", "tang_et_al")
+UNSUPPORTED_PRIORS = ("kde", "tang_et_al")
+#: the location-only baselines (range_amd/geo_baselines.py) and what ``prior`` is for each
+BASELINE_PRIORS = ("train_freq", "nn_dist", "nn_knn", "grid")
+_NEIGHBOR_PTYPE = {"nn_dist": "distance", "nn_knn": "knn"}
 
 
 def rank_counts(scores, labels) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -74,7 +79,10 @@ def compute_acc_batch(val_preds, val_classes, val_split, val_feats=None, train_c
     ``val_feats``: (N, 2) (lon, lat) DEGREES, as ``model(coords)`` takes them (the reference passes what its own
     data loader normalised).  ``prior_type='no_prior'`` ranks ``val_preds`` alone; ``prior`` a ``CspLocationModel``
     loaded with ``class_head=True`` and ``prior_type`` its ``spa_enc_type`` or ``'geo_net'`` ranks ``val_preds *
-    prior(val_feats)``, ``batch_size`` rows a call; any other ``prior_type`` raises NotImplementedError.  Logs the
+    prior(val_feats)``, ``batch_size`` rows a call; ``'train_freq'`` with ``prior`` the (num_classes,) array of
+    ``geo_baselines.train_freq_prior`` ranks ``val_preds * prior`` on the host; ``'nn_dist'`` / ``'nn_knn'`` with
+    ``prior`` a ``geo_baselines.NeighborPrior`` and ``'grid'`` with a ``geo_baselines.GridPrior`` rank ``val_preds *
+    prior(val_feats)`` on the GPU and drop no row; any other ``prior_type`` raises NotImplementedError.  Logs the
     reference's ``Top k acc (%)`` lines per split with its denominators (a sample the reference drops - no
     location - is a miss over the whole split) and returns its list of predicted classes, of the samples it keeps;
     with ``return_acc=True`` also ``{split: {k: accuracy in per cent}}``."""
@@ -106,9 +114,36 @@ def compute_acc_batch(val_preds, val_classes, val_split, val_feats=None, train_c
             ranks[sl], pred[sl] = prior.label_ranks(val_feats[sl], val_classes[sl],
                                                     None if val_preds is None else val_preds[sl])
         kept = ranks > 0
+    elif prior_type == "train_freq" and prior is not None:
+        freq = np.asarray(_host(prior), dtype=np.float64).reshape(1, -1)
+        ranks = np.zeros(N, dtype=np.int64)
+        pred = np.full(N, -1, dtype=np.int64)
+        for i in range(0, N, batch_size):
+            sl = slice(i, min(N, i + batch_size))
+            n = sl.stop - sl.start
+            blk = np.repeat(freq, n, axis=0) if val_preds is None else _host(val_preds[sl]).astype(np.float64) * freq
+            g, e, _ = rank_counts(blk, val_classes[sl])
+            if (g == -2).any():
+                raise ValueError("val_classes outside the classes of the prior")
+            ok = g >= 0
+            ranks[sl][ok] = 1 + g[ok].astype(np.int64) + e[ok]
+            pred[sl] = np.argmax(blk, axis=1)
+        kept = np.ones(N, dtype=bool)
+    elif prior_type in ("nn_dist", "nn_knn", "grid") and prior is not None and hasattr(prior, "label_ranks"):
+        if val_feats is None:
+            raise ValueError(f"prior_type={prior_type!r} needs val_feats, the (lon, lat) degrees")
+        extra = {"ptype": _NEIGHBOR_PTYPE[prior_type]} if prior_type in _NEIGHBOR_PTYPE else {}
+        ranks = np.zeros(N, dtype=np.int64)
+        pred = np.full(N, -1, dtype=np.int64)
+        for i in range(0, N, batch_size):
+            sl = slice(i, min(N, i + batch_size))
+            ranks[sl], pred[sl] = prior.label_ranks(val_feats[sl], val_classes[sl],
+                                                    None if val_preds is None else val_preds[sl], **extra)
+        kept = np.ones(N, dtype=bool)         # (a NaN location has the uniform prior; a NaN score has rank 0: a miss)
     else:
-        raise NotImplementedError(f"compute_acc_batch: prior_type={prior_type!r} is not implemented (only 'no_prior' and "
-                                  "a CSP prior: 'geo_net' or the model's spa_enc_type with prior a CspLocationModel)")
+        raise NotImplementedError(f"compute_acc_batch: prior_type={prior_type!r} is not implemented (only 'no_prior', a CSP "
+                                  "prior - 'geo_net' or the model's spa_enc_type with prior a CspLocationModel - and the "
+                                  "baselines 'train_freq', 'nn_dist', 'nn_knn', 'grid' with their prior objects)")
     logger.info(val_classes[kept].shape)
     acc = {}
     for ii, split in enumerate(np.unique(val_split)):

@@ -1036,4 +1036,89 @@ inline MapPlan map_plan(int64_t n, int c, int64_t max_grid = 0) {
     return p;
 }
 
+// The neighbour and grid geo priors (neighbor_kernel.h; include/range_neighbors.h).
+//   * vote scan: a workgroup of NEIGHBOR_VOTE_BLOCK threads owns a group of G consecutive queries, their int32 count
+//     rows (G * C * 4 bytes) in LDS beside NEIGHBOR_QUERY_LDS bytes of parameters a query.  G depends on C alone:
+//     as many rows as NEIGHBOR_COUNT_LDS holds, at most NEIGHBOR_MAX_GROUP (4 at C = 8142, 1 at the class cap
+//     NEIGHBOR_MAX_CLASSES = 32768, whose row is 128 KB of the CU's 160 KB).  The training points are walked in
+//     tiles of NEIGHBOR_BLOCK, dealt round-robin to `chunks` workgroups a group (grid y) when the groups alone do
+//     not reach NEIGHBOR_TARGET_WG; every chunk keeps a tile, there are at most NEIGHBOR_MAX_CHUNKS, and the
+//     partial count rows (chunks * groups * G * C int32) stay below NEIGHBOR_MAX_WS bytes.  With more than one
+//     chunk a fold launch (a workgroup a group) sums them and ranks.
+//   * k-th neighbour selection: a workgroup a query (grid-stride), NEIGHBOR_PASSES scans of the training set, one
+//     per NEIGHBOR_DIGIT_BITS-bit digit of the 64-bit key from the top (the first digit is the 9 bits left over),
+//     a 2^NEIGHBOR_DIGIT_BITS-bin histogram in LDS, then one ordered walk for the last tie.
+enum { NEIGHBOR_RADIUS = 0, NEIGHBOR_KNN = 1, NEIGHBOR_CELL = 2, NEIGHBOR_MODES = 3 };
+constexpr int NEIGHBOR_BLOCK = 256;                // a tile of training points; the selection's and the packing's workgroup
+constexpr int NEIGHBOR_VOTE_BLOCK = 1024;          // the vote scan's and the fold's workgroup: four tiles side by side
+constexpr int NEIGHBOR_MAX_GROUP = 8;
+constexpr int NEIGHBOR_MAX_CLASSES = 32768;
+constexpr size_t NEIGHBOR_COUNT_LDS = 132 * 1024;
+constexpr size_t NEIGHBOR_QUERY_LDS = 48;
+constexpr int NEIGHBOR_MAX_CHUNKS = 64;
+constexpr int64_t NEIGHBOR_TARGET_WG = 1024;
+constexpr int64_t NEIGHBOR_MAX_GRID = 1 << 16;
+constexpr int64_t NEIGHBOR_MAX_POINTS = (INT64_C(1) << 31) - 1;     // the counts are int32
+constexpr int64_t NEIGHBOR_MAX_QUERIES = (INT64_C(1) << 31) - 1;
+constexpr size_t NEIGHBOR_MAX_WS = (size_t)1 << 30;
+constexpr int NEIGHBOR_DIGIT_BITS = 11;
+constexpr int NEIGHBOR_PASSES = (64 + NEIGHBOR_DIGIT_BITS - 1) / NEIGHBOR_DIGIT_BITS;
+constexpr int NEIGHBOR_BINS = 1 << NEIGHBOR_DIGIT_BITS;
+
+struct NeighborPlan {
+    bool valid = false;
+    const char* why = "";
+    int block = NEIGHBOR_BLOCK, vote_block = NEIGHBOR_VOTE_BLOCK;
+    int group = 0;                      // G
+    int64_t groups = 0, n_tiles = 0;
+    unsigned grid = 0;                  // workgroups over the groups (grid x), walked grid-stride
+    int chunks = 0;                     // grid y
+    unsigned fold_grid = 0;             // chunks > 1: workgroups of the fold launch
+    size_t lds_bytes = 0;
+    size_t ws_ints = 0, ws_bytes = 0;   // chunks > 1: the partial count rows
+    unsigned select_grid = 0;           // workgroups of the selection, a query each, walked grid-stride
+    size_t select_lds = 0;
+    int64_t groups_of(int64_t x) const { return x < groups ? (groups - x + grid - 1) / grid : 0; }
+    int64_t tiles_of(int64_t y) const { return y < n_tiles ? (n_tiles - y + chunks - 1) / chunks : 0; }
+    // the bit shift of pass p's digit (the passes go from the top digit down)
+    static constexpr int shift_of(int pass) { return (NEIGHBOR_PASSES - 1 - pass) * NEIGHBOR_DIGIT_BITS; }
+};
+
+// queries a workgroup for C classes (0: C outside 1 .. NEIGHBOR_MAX_CLASSES)
+inline int neighbor_group(int C) {
+    if (C < 1 || C > NEIGHBOR_MAX_CLASSES) return 0;
+    return (int)std::min<size_t>(NEIGHBOR_MAX_GROUP, NEIGHBOR_COUNT_LDS / ((size_t)C * 4));
+}
+
+// B queries, N training points, C classes; k: neighbours of the selection (0: none asked for).  max_grid: 0 the
+// plan's choice, g > 0 at most g workgroups a launch and grid dimension.  chunks: 0 the plan's choice, n > 0 at
+// most n chunks (never more than the tiles, NEIGHBOR_MAX_CHUNKS or what the workspace cap allows).
+inline NeighborPlan neighbor_plan(int64_t B, int64_t N, int C, int64_t k, int64_t max_grid = 0, int chunks = 0) {
+    NeighborPlan p;
+    if (B < 1 || B > NEIGHBOR_MAX_QUERIES) { p.why = "B outside 1 .. 2^31 - 1"; return p; }
+    if (N < 1 || N > NEIGHBOR_MAX_POINTS) { p.why = "N outside 1 .. 2^31 - 1"; return p; }
+    if (C < 1 || C > NEIGHBOR_MAX_CLASSES) { p.why = "num_classes outside 1 .. 32768 (one count row of LDS)"; return p; }
+    if (k < 0 || k > N) { p.why = "k outside 1 .. N"; return p; }
+    if (max_grid < 0 || chunks < 0) { p.why = "max_grid or chunks below 0"; return p; }
+    const int64_t cap = max_grid > 0 ? std::min(max_grid, NEIGHBOR_MAX_GRID) : NEIGHBOR_MAX_GRID;
+    p.group = neighbor_group(C);
+    p.groups = (B + p.group - 1) / p.group;
+    p.n_tiles = (N + NEIGHBOR_BLOCK - 1) / NEIGHBOR_BLOCK;
+    p.grid = (unsigned)std::min(p.groups, cap);
+    const size_t row_ints = (size_t)p.groups * (size_t)p.group * (size_t)C;       // of one chunk
+    const int64_t want = chunks > 0 ? (int64_t)chunks : (NEIGHBOR_TARGET_WG + p.groups - 1) / p.groups;
+    const int64_t fits = std::max<int64_t>(1, (int64_t)(NEIGHBOR_MAX_WS / 4 / row_ints));
+    p.chunks = (int)std::min(std::min(std::min(want, p.n_tiles), std::min(fits, cap)), (int64_t)NEIGHBOR_MAX_CHUNKS);
+    p.lds_bytes = (((size_t)p.group * (size_t)C * 4 + 15) & ~(size_t)15) + (size_t)p.group * NEIGHBOR_QUERY_LDS;
+    if (p.chunks > 1) {
+        p.ws_ints = (size_t)p.chunks * row_ints;
+        p.ws_bytes = p.ws_ints * 4;
+        p.fold_grid = (unsigned)std::min(p.groups, cap);
+    }
+    p.select_grid = (unsigned)std::min(B, cap);
+    p.select_lds = (size_t)(NEIGHBOR_BINS + NEIGHBOR_BLOCK + 16) * 4;
+    p.valid = true;
+    return p;
+}
+
 }  // namespace range_host

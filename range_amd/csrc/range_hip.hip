@@ -32,6 +32,7 @@
 #include "csp_head_kernel.h"
 #include "csp_rank_kernel.h"
 #include "checker_kernel.h"
+#include "neighbor_kernel.h"
 
 using namespace range_hip;
 using namespace range_host;
@@ -164,6 +165,17 @@ struct range_ctx {
         DevBuf<double> ws_a;
         DevBuf<int64_t> ws_idx;
     } checker;
+    // range_set_neighbors: the packed training set of the neighbour / grid geo priors (neighbor_kernel.h), the
+    // chunks' partial count rows of a split scan, the selection of a k-nearest-neighbour call
+    struct Neighbors {
+        int64_t N = 0;                   // 0: no set installed
+        int C = 0;
+        bool hav = false, has_cells = false;
+        DevBuf<NeighborPoint> d_pts;
+        DevBuf<int32_t> ws_counts;
+        DevBuf<double> ws_redk;
+        DevBuf<int64_t> ws_jlast;
+    } nb;
     // words of host memory the kernels can write (hipHostMallocMapped; async_err.h): set by a persistent
     // kernel whose bounded wait for other workgroups gave up; read - without synchronising - by the
     // next call and behind every synchronising exit (check_async_error)
@@ -1662,3 +1674,4 @@ static void (*kept_stats_kernel_for(int n_pairs, bool geo))(KeptStatsArgs) {
 
 #include "csp_host.h"
 #include "checker_host.h"
+#include "neighbor_host.h"
