@@ -1,4 +1,5 @@
-// Host side of the checkerboard task's nearest-support scan (checker_kernel.h); part of range_hip.hip's translation unit.
+// Host side of the checkerboard task's nearest-support scan (checker_kernel.h).
+// Part of range_hip.hip's translation unit, behind engine_ctx.h.
 #pragma once
 
 extern "C" {

@@ -1,5 +1,5 @@
 // Host side of the CSP encoders, their class head and its evaluation (csp_kernel.h, csp_head_kernel.h, csp_rank_kernel.h).
-// Part of range_hip.hip's translation unit, at its place among the kernel tables (their order is the kernels').
+// Part of range_hip.hip's translation unit, behind engine_ctx.h.
 #pragma once
 
 // ---- the CSP location encoders (csp_kernel.h), by tile height (32 m_tiles rows) and activation

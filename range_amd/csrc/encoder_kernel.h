@@ -681,7 +681,7 @@ __device__ __forceinline__ void encoder_norm_query(const EncArgs& a, int64_t q, 
 // done, and from phase 2 on producers and consumers are the same K workgroups, resident by then;
 // a wait that does not end within ENC_SPIN_LIMIT polls (seconds) gives up instead of hanging - and
 // the tile's output rows are then NaN, the context's host-mapped error word is set, and the host
-// takes the separate-launch path from the next call on (range_hip.hip: check_async_error).
+// takes the separate-launch path from the next call on (engine_ctx.h: check_async_error).
 // The counters wrap to zero by themselves: arrivals + one increment per consumer = the wrap limit
 // of the atomic inc.
 constexpr uint32_t ENC_SPIN_LIMIT = 1u << 21;
@@ -707,7 +707,7 @@ __device__ __forceinline__ int enc_phase_sync(uint32_t* ctr, int n_prod, int n_c
         if (ok) {
             atomicInc(ctr, (uint32_t)(n_prod + n_cons - 1));     // (the last consumer's increment wraps the counter to 0)
         } else if (err) {
-            // say so where the host sees it without a synchronisation (range_hip.hip: check_async_error)
+            // say so where the host sees it without a synchronisation (engine_ctx.h: check_async_error)
             __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         *flag = ok;

@@ -215,13 +215,13 @@ inline std::vector<double> pack_weights(const double* W, int n_out, int k_in, co
     return out;
 }
 
-// ---- Launch plans: every number a launch site of range_hip.hip needs - which kernel variant, grid,
+// ---- Launch plans: every number a launch site of range_hip.hip's parts needs - which kernel variant, grid,
 // the argument fields derived from geometry, workspace sizes - as pure functions of integers and
-// switches.  range_hip.hip allocates, fills pointers and launches what a plan says;
+// switches.  The *_host.h parts allocate, fill pointers and launch what a plan says;
 // tests/native/host_sanitize.cpp asks the plans the cases the comments below state.
 
 // Integer constants of the kernel headers that the plans need.  The kernel headers keep the only
-// definition of each; range_hip.hip fills this struct from them once (PLAN_CONSTS).
+// definition of each; engine_ctx.h fills this struct from them once (PLAN_CONSTS).
 struct PlanConsts {
     int qtile, blk, val_dim, max_topk, p1_wg_per_cu;   // engine_prims.h: QTILE, BLK, VAL_DIM, MAX_TOPK; pass1.h: P1_WG_PER_CU
     int enc_qtile;                                     // encoder_kernel.h: ENC_QTILE
@@ -386,7 +386,7 @@ inline EncLaunchPlan plan_encoder(int n_cu, int n_slots, int H, int n_layers, bo
 //                      lists do not exist (top-k comes from the kept logits, or from range_topk_stream).
 // Temperatures must be finite, > 0 and <= MAX_TAU_SHARP (tau_geo <= 0: no geographic head); beyond
 // that the softmax is an argmax to float32 precision.  (include/range_hip.h: RANGE_MAX_TAU,
-// RANGE_MAX_TAU_SHARP are the same numbers; range_hip.hip asserts it.)
+// RANGE_MAX_TAU_SHARP are the same numbers; scan_host.h asserts it.)
 constexpr float MAX_TAU_CONSTANT = 43.0f;
 constexpr float MAX_TAU_SHARP = 1000.0f;
 enum ShiftMode { SHIFT_CONSTANT = 0, SHIFT_RUNNING_MAX = 1 };

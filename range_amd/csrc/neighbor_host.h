@@ -1,5 +1,5 @@
-// Host side of the neighbour and grid geo priors (neighbor_kernel.h; include/range_neighbors.h); part of
-// range_hip.hip's translation unit.
+// Host side of the neighbour and grid geo priors (neighbor_kernel.h; include/range_neighbors.h).
+// Part of range_hip.hip's translation unit, behind engine_ctx.h.
 #pragma once
 
 #include "../../include/range_neighbors.h"

@@ -1,5 +1,5 @@
 // Host side of the positional encoders (posenc_kernel.h): range_posenc_width, range_posenc_features.
-// Part of range_hip.hip's translation unit, at its place among the kernel tables (their order is the kernels').
+// Part of range_hip.hip's translation unit, behind engine_ctx.h.
 #pragma once
 
 // the positional encoders, by kind

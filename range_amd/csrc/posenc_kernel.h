@@ -176,3 +176,36 @@ __global__ __launch_bounds__(POSENC_BLOCK) void posenc_features_kernel(PosencArg
 }
 
 }  // namespace range_hip
+
+// Training-free coordinate encoders of the reference (range/range.py:262-272): one thread per
+// location, float64.  mode 0 'Direct' (:262-264): (lon,lat)*pi/180, evaluated as (x*pi)/180 like
+// the Python expression; mode 1 'Cartesian_3D' (:265-268, utils/utils.py:11-16): unit xyz of the
+// radians above; mode 2 'Wrap' (positional_encoding/wrap.py:20-29): cos/sin of torch.deg2rad(x)
+// = x * (pi/180) per column, ordered (cos lon, sin lon, cos lat, sin lat).
+// (range_coord_features, encoder_host.h; extern "C": the symbol is the plain name)
+extern "C" __global__ void coord_features_kernel(int mode, const double* __restrict__ lonlat, int64_t n,
+                                      double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double lon = lonlat[2 * i], lat = lonlat[2 * i + 1];
+    constexpr double PI = 3.141592653589793;
+    if (mode == 2) {
+        constexpr double PI_180 = 0.017453292519943295;
+        const double a = lon * PI_180, b = lat * PI_180;
+        out[4 * i + 0] = cos(a);
+        out[4 * i + 1] = sin(a);
+        out[4 * i + 2] = cos(b);
+        out[4 * i + 3] = sin(b);
+        return;
+    }
+    const double a = (lon * PI) / 180.0, b = (lat * PI) / 180.0;
+    if (mode == 0) {
+        out[2 * i + 0] = a;
+        out[2 * i + 1] = b;
+    } else {
+        const double cb = cos(b);
+        out[3 * i + 0] = cb * cos(a);
+        out[3 * i + 1] = cb * sin(a);
+        out[3 * i + 2] = sin(b);
+    }
+}

@@ -695,3 +695,31 @@ __global__ __launch_bounds__(256, 1) void topk_stream_bf16_kernel(TopkStreamArgs
 }
 
 }  // namespace range_hip
+
+// A plain one-launch streaming read of the same bytes the top-k scan streams (range_stream_read_timed,
+// topk_host.h): 16-byte non-temporal loads, 8 in flight per thread, 1 024 workgroups; the xor of everything
+// read goes to one word per workgroup so that the loads stay.
+// (extern "C": the symbol is the plain name)
+extern "C" __global__ __launch_bounds__(256) void stream_read_kernel(const range_hip::u32x4* __restrict__ p, int64_t n16, int passes,
+                                                          uint32_t* __restrict__ sink) {
+    using range_hip::u32x4;
+    // a workgroup reads 32 KB contiguous per step (8 loads of 16 bytes per thread, 4 KB apart)
+    const int64_t step = (int64_t)gridDim.x * 2048;
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    for (int ps = 0; ps < passes; ++ps) {
+        for (int64_t base = (int64_t)blockIdx.x * 2048; base < n16; base += step) {
+            u32x4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int64_t i = base + u * 256 + threadIdx.x;
+                v[u] = __builtin_nontemporal_load(p + (i < n16 ? i : n16 - 1));
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc ^= v[u];
+        }
+    }
+    uint32_t r = acc[0] ^ acc[1] ^ acc[2] ^ acc[3];
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) r ^= __shfl_xor(r, off);
+    if ((threadIdx.x & 63) == 0) atomicXor(sink + blockIdx.x, r);
+}

@@ -214,7 +214,7 @@ static void test_padding_and_host_parts() {
 }
 
 // ---- the launch plans (host_plan.h): the cases the comments of the plans state, and invariants over
-// a sweep of sizes.  The constants are the kernel headers' (range_hip.hip: PLAN_CONSTS).
+// a sweep of sizes.  The constants are the kernel headers' (engine_ctx.h: PLAN_CONSTS).
 static const PlanConsts KC{/*qtile*/ 64, /*blk*/ 16, /*val_dim*/ 1024, /*max_topk*/ 16, /*p1_wg_per_cu*/ 4, /*enc_qtile*/ 32,
                            /*topks_wl*/ 8, /*tg_qblock*/ 256, /*tg_wg_per_cu*/ 2, /*tg_cap_l*/ 32};
 static const int CU_COUNTS[] = {64, 80, 104, 128, 208, 256, 304};

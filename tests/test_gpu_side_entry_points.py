@@ -19,6 +19,7 @@ import torch
 import csp_head_refs as H
 import csp_refs as R
 from range_amd import _native, csp, posenc
+from refusal_table import RefusalTable
 from tools import synth
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,6 @@ DEV = "cuda:0"
 KIND = {"gridcell": posenc.KIND_GRID, "theory": posenc.KIND_THEORY}
 PROBS, SUM = _native.CSP_HEAD_PROBS, _native.CSP_HEAD_SUM
 NONE, F32, F64 = _native.CSP_IMG_NONE, _native.CSP_IMG_F32, _native.CSP_IMG_F64
-INVALID = -1
 
 NULL = "null argument"
 B_MSG = "B must be > 0"
@@ -66,15 +66,8 @@ def test_refusals_keep_code_and_text():
     idx, dist = z((4,), torch.int64), z((4,), torch.float64)
     freq = np.ones(2)
     fp = freq.ctypes.data
-    table = []
-
-    def rows(fn, ok, *faults):
-        """``faults``: (what, {argument index: value}, message) - ``ok`` with exactly those arguments replaced."""
-        for what, change, msg in faults:
-            args = list(ok)
-            for i, v in change.items():
-                args[i] = v
-            table.append((fn, what, args, msg))
+    table = RefusalTable()                # (every refusal of these entry points is RANGE_ERR_INVALID)
+    rows = table.rows
 
     rows("range_posenc_features", [h, posenc.KIND_THEORY, fp, 2, q, 4, feat, None],
          ("ctx", {0: None}, NULL), ("freq", {2: None}, NULL), ("lonlat", {4: None}, NULL), ("out", {6: None}, NULL),
@@ -126,9 +119,7 @@ def test_refusals_keep_code_and_text():
          ("q + 4", {1: q + 4}, NEAR_ALIGN), ("sup + 4", {3: sup + 4}, NEAR_ALIGN), ("idx + 4", {7: idx + 4}, NEAR_ALIGN),
          ("dist + 4", {8: dist + 4}, NEAR_ALIGN))
     assert len(table) == 88
-    for fn, what, args, msg in table:
-        rc = getattr(lib, fn)(*args)
-        assert (rc, lib.range_last_error().decode()) == (INVALID, msg), (fn, what)
+    table.check(lib)
     torch.cuda.synchronize()
 
 

@@ -64,6 +64,13 @@ def test_inner_loop_of_the_recompute_pass2():
     assert not moved, moved[:4]
 
 
+def _cuid_object(cuid):
+    """What closes a listing: the object hipcc names after a hash of the translation unit's sources."""
+    return (f"\t.text\n\t.p2alignl 6, 3212836864\n\t.type\t__hip_cuid_{cuid},@object\n\t.section\t.bss,\"aw\",@nobits\n"
+            f"\t.globl\t__hip_cuid_{cuid}\n__hip_cuid_{cuid}:\n\t.byte\t0\n\t.size\t__hip_cuid_{cuid}, 1\n"
+            f"\t.addrsig_sym __hip_cuid_{cuid}\n")
+
+
 def _listing(cuid):
     """A listing of two kernels in hipcc's layout, closed by the translation unit's ``__hip_cuid`` object."""
     def kernel(name, body):
@@ -73,10 +80,7 @@ def _listing(cuid):
                 f"\t.end_amdhsa_kernel\n\t.text\n.Lfunc_end0:\n\t.size\t{name}, .Lfunc_end0-{name}\n"
                 f"\t.set {name}.num_vgpr, 8\n\t.section\t.AMDGPU.csdata,\"\",@progbits\n; Kernel info:\n"
                 f"; NumVgprs: 8\n; NumAgprs: 0\n; ScratchSize: 0\n; Occupancy: 8\n")
-    return (kernel("first_kernel", "\tv_mov_b32_e32 v0, 0\n") + kernel("last_kernel", "\tv_mov_b32_e32 v1, 1\n") +
-            f"\t.text\n\t.p2alignl 6, 3212836864\n\t.type\t__hip_cuid_{cuid},@object\n\t.section\t.bss,\"aw\",@nobits\n"
-            f"\t.globl\t__hip_cuid_{cuid}\n__hip_cuid_{cuid}:\n\t.byte\t0\n\t.size\t__hip_cuid_{cuid}, 1\n"
-            f"\t.addrsig_sym __hip_cuid_{cuid}\n")
+    return kernel("first_kernel", "\tv_mov_b32_e32 v0, 0\n") + kernel("last_kernel", "\tv_mov_b32_e32 v1, 1\n") + _cuid_object(cuid)
 
 
 def test_asm_diff_ends_a_kernel_at_its_own_end(tmp_path, capsys):
@@ -94,5 +98,38 @@ def test_asm_diff_ends_a_kernel_at_its_own_end(tmp_path, capsys):
     assert "differs" not in out and "2 identical" in out
     # a change inside a kernel is still one
     (tmp_path / "b.s").write_text(b.replace("v_mov_b32_e32 v1, 1", "v_mov_b32_e32 v1, 2"))
+    kernel_asm_diff.main(["kernel_asm_diff", str(tmp_path / "a.s"), str(tmp_path / "b.s")])
+    assert "differs: last_kernel" in capsys.readouterr().out
+
+
+def _loop_kernel(name, f, op):
+    """A kernel with a loop, in hipcc's layout, emitted as the ``f``-th function of its listing."""
+    return (f"\t.text\n\t.protected\t{name}\n\t.globl\t{name}\n\t.type\t{name},@function\n"
+            f"{name}:\n.Lfunc_begin{f}:\n; %bb.0:\n\ts_mov_b32 s0, 0\n.LBB{f}_1:\n\t{op}\n\ts_add_i32 s0, s0, 1\n"
+            f"\ts_cmp_lt_i32 s0, 8\n\ts_cbranch_scc1 .LBB{f}_1\n; %bb.2:                ; %exit, from BB{f}_1\n\ts_endpgm\n"
+            f"\t.section\t.rodata,\"a\",@progbits\n\t.amdhsa_kernel {name}\n\t\t.amdhsa_next_free_vgpr 8\n"
+            f"\t.end_amdhsa_kernel\n\t.text\n.Lfunc_end{f}:\n\t.size\t{name}, .Lfunc_end{f}-{name}\n"
+            f"\t.set {name}.num_vgpr, 8\n\t.section\t.AMDGPU.csdata,\"\",@progbits\n; Kernel info:\n"
+            f"; NumVgprs: 8\n; NumAgprs: 0\n; ScratchSize: 0\n; Occupancy: 8\n")
+
+
+def test_asm_diff_is_independent_of_emission_order(tmp_path, capsys):
+    """The same two kernels emitted in swapped order carry each other's function ordinal in their local labels
+    (.LBB<f>_<n>, BB<f>_<n> in comments, .Lfunc_begin<f> / .Lfunc_end<f>) and differ in nothing else: no kernel
+    differs.  A changed instruction inside one of them still does, and the block number is still compared."""
+    x, y = "v_add_f32_e32 v0, v0, v1", "v_mul_f32_e32 v0, v0, v1"
+    a = _loop_kernel("first_kernel", 0, x) + _loop_kernel("last_kernel", 1, y) + _cuid_object("48af349932bb732f")
+    b = _loop_kernel("last_kernel", 0, y) + _loop_kernel("first_kernel", 1, x) + _cuid_object("48af349932bb732f")
+    assert ".LBB0_1" in a and "BB1_1" in a and ".Lfunc_end1-last_kernel" in a
+    (tmp_path / "a.s").write_text(a)
+    (tmp_path / "b.s").write_text(b)
+    assert kernel_asm_diff.main(["kernel_asm_diff", str(tmp_path / "a.s"), str(tmp_path / "b.s")]) == 0
+    out = capsys.readouterr().out
+    assert "differs" not in out and "2 / 2 kernel symbols, 2 identical" in out
+    (tmp_path / "b.s").write_text(b.replace(x, "v_sub_f32_e32 v0, v0, v1"))
+    kernel_asm_diff.main(["kernel_asm_diff", str(tmp_path / "a.s"), str(tmp_path / "b.s")])
+    out = capsys.readouterr().out
+    assert "differs: first_kernel" in out and "differs: last_kernel" not in out and "1 identical" in out
+    (tmp_path / "b.s").write_text(b.replace("s_cbranch_scc1 .LBB0_1", "s_cbranch_scc1 .LBB0_2"))
     kernel_asm_diff.main(["kernel_asm_diff", str(tmp_path / "a.s"), str(tmp_path / "b.s")])
     assert "differs: last_kernel" in capsys.readouterr().out

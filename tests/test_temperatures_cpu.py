@@ -100,7 +100,7 @@ def test_codegen_of_the_running_max_pass1():
         assert regs["sharp"][0] + regs["sharp"][1] <= 128 and regs["sharp"][2] >= 4, f"registers (vgpr, agpr, occupancy): {regs}"
         mf = lambda k: len(re.findall(r"\n\s*v_mfma_f32_16x16x4_f32\b", k))
         assert mf(s) == mf(p) == (65 if geo == "1" else 64), (mf(s), mf(p))
-    src = open(os.path.join(REPO, "range_amd", "csrc", "range_hip.hip")).read()
+    src = open(os.path.join(REPO, "range_amd", "csrc", "scan_host.h")).read()
     assert re.search(r"launch\(kernel, dim3\(\(unsigned\)p\.grid\), dim3\(256\), SCAN_LDS_BYTES", src), seen
 
 

@@ -48,7 +48,7 @@ _HASH_A, _HASH_B, _HASH_P = 1_000_003, 7_919, 2_147_483_647
 
 
 def k_shift(tau: float) -> np.float32:
-    """The kernels' shift m = k = (float)(tau * log2 e) (range_hip.hip: k_sem / k_geo)."""
+    """The kernels' shift m = k = (float)(tau * log2 e) (scan_host.h: softmax_scales, k_sem / k_geo)."""
     return np.float32(float(np.float32(tau)) * LOG2E)
 
 

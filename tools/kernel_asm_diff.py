@@ -7,8 +7,10 @@ For a refactor that must not change the generated code.  Per kernel symbol: iden
 those that differ NumVgprs / NumAgprs / ScratchSize / Occupancy of both sides and, for the innermost
 backward-branch region that holds an MFMA, the instruction counts, whether the register-masked
 instruction sequence is equal and whether the opcode multiset is equal.  Exit status 1 if the symbol
-sets differ, or if ScratchSize, NumAgprs or Occupancy differ anywhere.  It compares what is there; it
-looks for no particular instruction.
+sets differ, or if ScratchSize, NumAgprs or Occupancy differ anywhere.  Kernels are compared independent
+of the order the compiler emitted them in (the function ordinal of local labels is masked), so moving a
+kernel table or an include in the source is no difference.  It compares what is there; it looks for no
+particular instruction.
 """
 import collections
 import re
@@ -19,10 +21,10 @@ FIELDS = ("NumVgprs", "NumAgprs", "ScratchSize", "Occupancy")
 
 def innermost_mfma_loop(body):
     """Lines of the shortest backward-branch region of ``body`` that contains an MFMA."""
-    labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"(\.LBB\d+_\d+):", l)] if m}
+    labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"(\.LBB[\d#]+_\d+):", l)] if m}
     best = None
     for i, l in enumerate(body):
-        m = re.match(r"\s+s_c?branch\S*\s+(\.LBB\d+_\d+)", l)
+        m = re.match(r"\s+s_c?branch\S*\s+(\.LBB[\d#]+_\d+)", l)
         if m and labels.get(m.group(1), i) < i:
             region = body[labels[m.group(1)]:i + 1]
             if any(re.match(r"\s+v_mfma", r) for r in region) and (best is None or len(region) < len(best)):
@@ -44,14 +46,21 @@ def own_end(name, lines):
     return n
 
 
+def without_ordinal(text):
+    """Local labels carry the ordinal of their function in the listing (``.LBB<f>_<n>``, ``BB<f>_<n>`` in
+    LLVM's comments, ``.Lfunc_begin<f>`` / ``.Lfunc_end<f>``): the order in which the compiler emitted the
+    kernels, which follows the order of the source.  A fixed token takes its place; the block number stays."""
+    return re.sub(r"(\.LBB|\bBB|\.Lfunc_begin|\.Lfunc_end)\d+(?=_\d|\b)", r"\1#", text)
+
+
 def kernels(text):
-    """{symbol: text from its label to its own end} for every kernel of a listing."""
+    """{symbol: text from its label to its own end, without function ordinals} for every kernel of a listing."""
     chunks = re.split(r"\n(?=[A-Za-z_][\w$.]*:)", text)
     out = {}
     for c in chunks:
         if re.search(r"^\s*\.amdhsa_kernel\s", c, re.M):
             name, lines = c.split(":", 1)[0], c.split("\n")
-            out[name] = "\n".join(lines[:own_end(name, lines)])
+            out[name] = without_ordinal("\n".join(lines[:own_end(name, lines)]))
     return out
 
 
@@ -63,7 +72,7 @@ def instructions(lines):
 
 def masked(code):
     """Register numbers and local labels replaced: what is left is opcodes, operand kinds, immediates."""
-    return [re.sub(r"\.LBB\d+_\d+", "L", re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1#", c)) for c in code]
+    return [re.sub(r"\.LBB[\d#]+_\d+", "L", re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", r"\1#", c)) for c in code]
 
 
 def main(argv):

@@ -51,10 +51,10 @@ def main():
     for i, (w, b) in enumerate(zip(enc.weights, enc.biases)):
         print(f"  layer {i}: weight {tuple(w.shape)} {w.dtype}, |w| max {np.abs(w).max():.3e}, bias {tuple(b.shape)}")
     if not 1 <= L <= 64:
-        fail(f"legendre_polys={L}: the encoder kernel covers 1..64 (range_amd/csrc/range_hip.hip: range_set_encoder)")
+        fail(f"legendre_polys={L}: the encoder kernel covers 1..64 (range_amd/csrc/encoder_host.h: range_set_encoder)")
     if not 1 <= H <= 1024:
         fail(f"capacity H={H}: the encoder kernel covers hidden widths up to 1024 (the hidden activations of a 16-query "
-             "workgroup live in LDS: 16 x H float64 <= 128 KB; range_amd/csrc/range_hip.hip: range_set_encoder)")
+             "workgroup live in LDS: 16 x H float64 <= 128 KB; range_amd/csrc/encoder_host.h: range_set_encoder)")
     Hk = (H + 63) // 64 * 64 if H <= 512 else (768 if H <= 768 else 1024)
     if Hk != H:
         print(f"  capacity H={H} runs zero-padded as the kernel width {Hk} (same result bit for bit, {Hk / H:.2f}x the first-layer work)")
