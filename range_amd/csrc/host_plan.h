@@ -1121,4 +1121,138 @@ inline NeighborPlan neighbor_plan(int64_t B, int64_t N, int C, int64_t k, int64_
     return p;
 }
 
+// The cluster map (cluster_kernels.h; include/range_cluster.h): complete-linkage clustering of n unit rows of d
+// features through their n x n float64 distance matrix.
+//   * normalise: a wave a row, CLUSTER_NORM_ROWS rows a trip of a workgroup of CLUSTER_BLOCK threads;
+//   * distances: the GEMM's lower triangle is finished in tiles of CLUSTER_TILE x CLUSTER_TILE, a workgroup a tile
+//     of the tile triangle (tj <= ti), which also writes the mirrored tile;
+//   * linkage rounds: the row scan takes a workgroup a stale row; the merges walk items of (pair, chunk of
+//     CLUSTER_CHUNK columns); the three list kernels (stale rows, reciprocal pairs, deactivation) are one workgroup of
+//     CLUSTER_SERIAL_BLOCK threads, thread t owning the rows [t * serial_rows, (t + 1) * serial_rows) so that its
+//     lists come out in ascending row order.
+// Every grid is capped at CLUSTER_MAX_GRID (or max_grid) workgroups and walks its items grid-stride; no result
+// depends on the grid.  The workspace holds the linkage state at the byte offsets below.
+constexpr int CLUSTER_BLOCK = 256;
+constexpr int CLUSTER_NORM_ROWS = CLUSTER_BLOCK / 64;
+constexpr int CLUSTER_NORM_REGS = 32;              // a lane keeps up to 32 entries of its row: rows of d <= 2048 are read once
+constexpr int CLUSTER_TILE = 64;
+constexpr int CLUSTER_CHUNK = 1024;
+constexpr int CLUSTER_SERIAL_BLOCK = 1024;
+constexpr int64_t CLUSTER_MAX_GRID = 4096;
+constexpr int64_t CLUSTER_MAX_ROWS = INT64_C(1) << 17;     // 2^17 rows: a 137 GB matrix
+constexpr int CLUSTER_MAX_D = 1 << 20;
+
+struct ClusterPlan {
+    bool valid = false;
+    int block = CLUSTER_BLOCK, serial_block = CLUSTER_SERIAL_BLOCK;
+    int64_t norm_groups = 0;            // row groups of the normaliser
+    unsigned norm_grid = 0;
+    int64_t tiles = 0, fin_items = 0;   // tiles a side; tiles of the triangle
+    unsigned fin_grid = 0;
+    unsigned scan_grid = 0;             // workgroups of the first scan (later ones: min(active rows, cap))
+    int64_t chunks = 0;                 // column chunks of a row
+    int64_t serial_rows = 0;            // rows a thread of the list kernels owns
+    int64_t cap = 0;
+    size_t matrix_bytes = 0;            // n * n * 8: the caller's D
+    // workspace: bytes from its start
+    size_t off_active = 0, off_stale = 0, off_mrow = 0, off_nn = 0, off_nnd = 0, off_list = 0, off_pi = 0, off_pj = 0,
+           off_counters = 0, ws_bytes = 0;
+    // grid of a launch over `items` work items
+    unsigned grid_of(int64_t items) const { return (unsigned)std::max<int64_t>(1, std::min(items, cap)); }
+    int64_t items_of(int64_t x, int64_t items, int64_t grid) const { return x < items ? (items - x + grid - 1) / grid : 0; }
+};
+
+// Invalid: n outside 1 .. 2^17, d outside 1 .. 2^20, a negative max_grid.  (One row has a plan - the normaliser
+// takes it - but no linkage.)
+inline ClusterPlan cluster_plan(int64_t n, int64_t d, int64_t max_grid = 0) {
+    ClusterPlan p;
+    if (n < 1 || n > CLUSTER_MAX_ROWS || d < 1 || d > CLUSTER_MAX_D || max_grid < 0) return p;
+    p.cap = max_grid > 0 ? std::min(max_grid, CLUSTER_MAX_GRID) : CLUSTER_MAX_GRID;
+    p.norm_groups = (n + CLUSTER_NORM_ROWS - 1) / CLUSTER_NORM_ROWS;
+    p.norm_grid = p.grid_of(p.norm_groups);
+    p.tiles = (n + CLUSTER_TILE - 1) / CLUSTER_TILE;
+    p.fin_items = p.tiles * (p.tiles + 1) / 2;
+    p.fin_grid = p.grid_of(p.fin_items);
+    p.scan_grid = p.grid_of(n);
+    p.chunks = (n + CLUSTER_CHUNK - 1) / CLUSTER_CHUNK;
+    p.serial_rows = (n + CLUSTER_SERIAL_BLOCK - 1) / CLUSTER_SERIAL_BLOCK;
+    p.matrix_bytes = (size_t)n * (size_t)n * sizeof(double);
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t nb = up((size_t)n), half = up((size_t)(n / 2 + 1) * 4);
+    p.off_active = 0;
+    p.off_stale = p.off_active + nb;
+    p.off_mrow = p.off_stale + nb;
+    p.off_nn = p.off_mrow + nb;
+    p.off_nnd = p.off_nn + up((size_t)n * 4);
+    p.off_list = p.off_nnd + (size_t)n * 8;
+    p.off_pi = p.off_list + up((size_t)n * 4);
+    p.off_pj = p.off_pi + half;
+    p.off_counters = p.off_pj + half;
+    p.ws_bytes = p.off_counters + 64;
+    p.valid = true;
+    return p;
+}
+
+// The tile (ti, tj <= ti) of item t of the tile triangle, rows first: t = ti (ti + 1) / 2 + tj.
+RANGE_HD void cluster_tile_of(int64_t t, int64_t& ti, int64_t& tj) {
+    int64_t r = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((r + 1) * (r + 2) / 2 <= t) ++r;
+    while (r * (r + 1) / 2 > t) --r;
+    ti = r;
+    tj = t - r * (r + 1) / 2;
+}
+
+// The cut of a complete-linkage tree.  merges (n - 1, 2) and heights (n - 1) are the device's merge record in
+// emission order: pair t joined the clusters that then held rows merges[2t] and merges[2t + 1] at height heights[t].
+// The merges are sorted stably by height - parents follow their children: heights are monotone under complete
+// linkage, and at equal heights a child was emitted in an earlier round - and
+//   * labels (n, may be null): the first n - k sorted merges are applied by union-find and the clusters numbered by
+//     first occurrence (the cluster of row 0 is 0, the next new one met going down the rows is 1, ...);
+//   * Z (n - 1, 4, may be null): scipy's linkage matrix of all of them - the two cluster ids (a row, or n + s for the
+//     cluster sorted merge s made; the smaller first), the height, the new cluster's size.
+// False: n < 1, k outside 1 .. n, a row index outside 0 .. n - 1, or a merge inside one cluster.
+inline bool cluster_cut(int64_t n, const int32_t* merges, const double* heights, int64_t k, int32_t* labels, double* Z) {
+    if (n < 1 || k < 1 || k > n || (n > 1 && (!merges || !heights))) return false;
+    const int64_t m = n - 1;
+    std::vector<int64_t> order((size_t)m);
+    for (int64_t t = 0; t < m; ++t) order[(size_t)t] = t;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return heights[a] < heights[b]; });
+    std::vector<int64_t> parent((size_t)n), id((size_t)n), size((size_t)n, 1);
+    for (int64_t i = 0; i < n; ++i) parent[(size_t)i] = id[(size_t)i] = i;
+    auto find = [&](int64_t x) {
+        int64_t r = x;
+        while (parent[(size_t)r] != r) r = parent[(size_t)r];
+        while (parent[(size_t)x] != r) { const int64_t nx = parent[(size_t)x]; parent[(size_t)x] = r; x = nx; }
+        return r;
+    };
+    auto number = [&]() {
+        std::vector<int32_t> of_root((size_t)n, -1);
+        int32_t next = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t r = find(i);
+            if (of_root[(size_t)r] < 0) of_root[(size_t)r] = next++;
+            labels[i] = of_root[(size_t)r];
+        }
+    };
+    if (labels && n - k == 0) number();
+    for (int64_t s = 0; s < m; ++s) {
+        const int64_t t = order[(size_t)s];
+        const int64_t a = merges[2 * t], b = merges[2 * t + 1];
+        if (a < 0 || a >= n || b < 0 || b >= n) return false;
+        const int64_t ra = find(a), rb = find(b);
+        if (ra == rb) return false;
+        if (Z) {
+            Z[4 * s + 0] = (double)std::min(id[(size_t)ra], id[(size_t)rb]);
+            Z[4 * s + 1] = (double)std::max(id[(size_t)ra], id[(size_t)rb]);
+            Z[4 * s + 2] = heights[t];
+            Z[4 * s + 3] = (double)(size[(size_t)ra] + size[(size_t)rb]);
+        }
+        parent[(size_t)rb] = ra;
+        size[(size_t)ra] += size[(size_t)rb];
+        id[(size_t)ra] = n + s;
+        if (labels && s + 1 == n - k) number();
+    }
+    return true;
+}
+
 }  // namespace range_host

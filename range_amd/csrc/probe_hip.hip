@@ -18,12 +18,27 @@ struct range_probe_ctx {
     int n_cu = 256;
     DevBuf<double> ws_slabs, ws_part, ws_A, d_ntr, d_alphas;
     DevBuf<double> ws_map;   // the ICA step's slabs (map_host.h), sized by range_map_reserve
+    DevBuf<uint8_t> ws_cluster;   // the linkage state (cluster_host.h), sized by range_cluster_reserve
+    double cluster_ms[2] = {0.0, 0.0};   // the last linkage: first round, the other rounds (host clock)
     DevBuf<int32_t> d_info;
 };
 
 namespace {
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Split-K slabs of one GEMM of `tiles` tiles (batch == 1, when the tile count alone cannot fill the chip);
+// k_chunk: the K range of a slab.
+int gemm_splits(const range_probe_ctx* c, int tiles, int K, int batch, int& k_chunk) {
+    int splits = 1;
+    if (batch == 1 && K >= 2 * 512) {
+        // two full rounds of the chip's 2 * n_cu workgroup slots, never a nearly empty third one
+        const int slots = 2 * c->n_cu;
+        splits = std::min(K / 512, std::max(1, 2 * slots / tiles));
+    }
+    k_chunk = cdiv(cdiv(K, splits), GEMM_KT) * GEMM_KT;
+    return std::max(1, cdiv(K, k_chunk));
+}
 
 // One GEMM (batch == 1, split-K slabs when the tile count alone cannot fill the chip) or a batch
 // of equally shaped GEMMs (blockIdx.z).
@@ -33,14 +48,7 @@ int launch_gemm(range_probe_ctx* c, GemmArgs g, bool a_kc, bool b_kc, int batch,
     const int tiles = g.lower_only ? tiles_m * (tiles_m + 1) / 2 : tiles_m * tiles_n;
     g.tiles_n = tiles_n;
     if (g.batch_inner <= 0) g.batch_inner = 1;
-    int splits = 1;
-    if (batch == 1 && g.K >= 2 * 512) {
-        // two full rounds of the chip's 2 * n_cu workgroup slots, never a nearly empty third one
-        const int slots = 2 * c->n_cu;
-        splits = std::min(g.K / 512, std::max(1, 2 * slots / tiles));
-    }
-    g.k_chunk = cdiv(cdiv(g.K, splits), GEMM_KT) * GEMM_KT;
-    splits = std::max(1, cdiv(g.K, g.k_chunk));
+    const int splits = gemm_splits(c, tiles, g.K, batch, g.k_chunk);
     double* dst = g.C;
     const int64_t ldd = g.ldc;
     const double beta = g.beta;
@@ -350,3 +358,5 @@ int range_probe_accuracy(range_probe_ctx* c, const double* P, const double* c0, 
 
 // the embedding map's entry points (include/range_map.h)
 #include "map_host.h"
+// the cluster map's entry points (include/range_cluster.h)
+#include "cluster_host.h"

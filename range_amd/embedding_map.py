@@ -206,10 +206,11 @@ def _fit(eng, dev, feats, n, d, c, seed, max_iter, tol, nbins, return_info):
     return (out, info) if return_info else out
 
 
-def embedding_map(model, locs, batch_size: int = 100000, **kw):
-    """``ica_colors`` of ``model``'s embeddings of ``locs`` (N, 2) (lon, lat): the locations are encoded
-    ``batch_size`` at a time (with ``return_device=True`` where the model's forward has it) straight into the one
-    float64 device matrix the fit then runs on.  Keyword arguments go to ``ica_colors``."""
+def embed_locations(model, locs, batch_size: int = 100000, device=None):
+    """(feats, device): ``model``'s embeddings of ``locs`` (N, 2) (lon, lat) as one float64 (N, D) device matrix.  The
+    locations are encoded ``batch_size`` at a time (with ``return_device=True`` where the model's forward has it)
+    straight into that matrix; ``device`` defaults to the model's engine's.  The loop of ``embedding_map`` and
+    ``cluster_map``."""
     import inspect
     locs = np.asarray(locs) if not isinstance(locs, torch.Tensor) else locs
     if locs.ndim != 2 or locs.shape[1] != 2 or locs.shape[0] < 2:
@@ -221,7 +222,7 @@ def embedding_map(model, locs, batch_size: int = 100000, **kw):
         on_device = "return_device" in inspect.signature(fwd).parameters
     except (TypeError, ValueError):
         on_device = False
-    dev = kw.get("device")
+    dev = device
     if dev is None:
         eng = getattr(model, "engine", None)
         dev = eng.device if eng is not None else "cuda"
@@ -236,5 +237,11 @@ def embedding_map(model, locs, batch_size: int = 100000, **kw):
             if feats is None:
                 feats = torch.empty((n, e.shape[1]), dtype=torch.float64, device=dev)
             feats[i:i + e.shape[0]].copy_(e)           # (widens float32, uploads a host result)
-    kw["device"] = dev
+    return feats, dev
+
+
+def embedding_map(model, locs, batch_size: int = 100000, **kw):
+    """``ica_colors`` of ``model``'s embeddings of ``locs`` (N, 2) (lon, lat), encoded by ``embed_locations`` into the
+    one float64 device matrix the fit then runs on.  Keyword arguments go to ``ica_colors``."""
+    feats, kw["device"] = embed_locations(model, locs, batch_size, kw.get("device"))
     return ica_colors(feats, **kw)
