@@ -524,7 +524,15 @@ int range_finalize(range_ctx* ctx, const float* partials_dev, int32_t n_parts,
  * Replaces LocationEncoder.forward for 'RANGE' / 'RANGE+' (range/range.py:206-240) up to the
  * final device->host copy, which stays in the Python shim.
  *   model : RANGE_MODEL_RANGE (tau 15) | RANGE_MODEL_RANGE_PLUS (tau 12 / 40, beta blend)
- *   out_dev : (B,1280) float64 */
+ *   out_dev : (B,1280) float64
+ * A batch of several rounds of pass 2 against a bank beyond the stream-K walk (exact w @ V, temperatures
+ * up to RANGE_MAX_TAU, logits kept) runs in chunks of query tiles: pass 1 of chunk i + 1 on a second,
+ * non-blocking stream of the context, on the CUs that pass 2 of chunk i occupies; every chunk with the
+ * whole batch's split counts, so the result is that of one launch per pass, bit for bit.  `stream` waits
+ * for all of that work before the call's last pass 2: what the caller enqueues on it afterwards orders as
+ * behind a forward of one stream, and no synchronisation is added.  The kept logits end complete
+ * (range_kept_queries() == B).  RANGE_FWD_OVERLAP=0 in the environment: never in chunks (A/B);
+ * RANGE_FWD_OVERLAP=n: chunks of n query tiles (tests). */
 int range_forward(range_ctx* ctx, const double* lonlat_dev, int64_t B, int32_t model, float beta,
                   double* out_dev, range_stream_t stream);
 
@@ -550,7 +558,9 @@ int range_forward_host(range_ctx* ctx, const double* lonlat_dev, int64_t B, int3
  * driver to fill fresh result arrays from pinned staging memory). */
 int range_host_copy(range_ctx* ctx, void* dst, const void* src, size_t bytes);
 
-/* Introspection for the bench harness: launch geometry of the last scan/attend launch. */
+/* Introspection for the bench harness: launch geometry of the last scan/attend launch.  After a
+ * range_forward in chunks: the forward's whole geometry - all its query tiles, the split count every
+ * chunk's pass 2 ran with. */
 int range_last_attend_geometry(const range_ctx* ctx, int32_t* n_query_tiles, int32_t* n_splits);
 
 /* Per-kernel device timing with HIP events recorded on the launch stream, around the kernel

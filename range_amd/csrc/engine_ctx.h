@@ -16,6 +16,10 @@ struct Switches {
     bool topk_gemm = true;           // RANGE_TOPK_GEMM=0: batches beyond 256 queries through the streaming scan too (A/B)
     int tg_sample = TG_SAMPLE;       // RANGE_TG_SAMPLE=n: pass A of the batch top-k looks at every n-th tile (tuning)
     bool p2_streamk = true;          // RANGE_P2_STREAMK=0: pass 2 as one workgroup per (bank split, query tile) (A/B)
+    // RANGE_FWD_OVERLAP: range_forward in chunks of query tiles, pass 1 of the next chunk beside pass 2 (host_plan.h:
+    // plan_forward_chunks).  Unset (-1): the plan's rule; 0: never (A/B, the tests' yardstick); n > 0: chunks of n
+    // query tiles whatever the rule says (tests of the path at small sizes)
+    int fwd_overlap = -1;
 };
 
 static Switches parse_switches() {
@@ -30,6 +34,7 @@ static Switches parse_switches() {
     if (const char* e = std::getenv("RANGE_TOPK_GEMM")) sw.topk_gemm = e[0] != '0';
     if (const char* e = std::getenv("RANGE_TG_SAMPLE")) sw.tg_sample = std::max(1, std::min(16, std::atoi(e)));
     if (const char* e = std::getenv("RANGE_P2_STREAMK")) sw.p2_streamk = e[0] != '0';
+    if (const char* e = std::getenv("RANGE_FWD_OVERLAP")) sw.fwd_overlap = std::max(0, std::atoi(e));
     return sw;
 }
 
@@ -156,6 +161,12 @@ struct range_ctx {
         hipStream_t copy_stream = nullptr;
         std::unique_ptr<HostCopyPool> pool;
     } host;
+    // range_forward in chunks (forward_host.h): the stream of the later chunks' pass 1 and the events between it
+    // and the caller's stream - [0] chunk 0 scanned, [i] the statistics of chunk i merged; created on first use
+    struct Overlap {
+        hipStream_t aux_stream = nullptr;
+        std::vector<hipEvent_t> events;
+    } ovl;
     // profiling: event pairs per kernel kind
     struct Profiling {
         bool on = false;
@@ -172,6 +183,8 @@ struct range_ctx {
         if (host.h_stage) (void)hipHostFree(host.h_stage);
         if (h_async_err) (void)hipHostFree(h_async_err);
         if (host.copy_stream) (void)hipStreamDestroy(host.copy_stream);
+        if (ovl.aux_stream) (void)hipStreamDestroy(ovl.aux_stream);
+        for (auto e : ovl.events) (void)hipEventDestroy(e);
         for (auto& v : prof.pairs) for (auto& p : v) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
         for (auto e : ev_pool) (void)hipEventDestroy(e);
     }

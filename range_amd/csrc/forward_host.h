@@ -78,6 +78,79 @@ static int attend_workspace(range_ctx* c, int64_t p0, int64_t p1, const ModelPar
                        c->pass.ws_stats.p + p0 * 4, nullptr, map, kept ? p0 : -1, stream);
 }
 
+// The two passes of the workspace's B queries in the chunks of `plan` (host_plan.h: plan_forward_chunks), the result
+// into `out`.  On the caller's stream: pass 1 of chunk 0 as scan_stats_kernel, then per chunk pass 2 and finalize;
+// on the context's auxiliary stream, behind chunk 0's pass 1: pass 1 of chunks 1 .. as the kernel that shares a CU
+// with pass 2 (pass1_beside.h), each followed by its merge and an event that pass 2 of the chunk waits for.  The
+// caller's stream so waits for every piece of auxiliary work in front of the last chunk's pass 2: what the caller
+// enqueues afterwards orders as behind a forward of one stream, and the next call's auxiliary work (behind that
+// call's chunk 0) orders behind this call's.  Statistics parts have a region per chunk (chunk i + 1 scans while chunk
+// i merges); the slabs are reused chunk after chunk: pass 2 and finalize share a stream.
+// *chunked false: chunk 0 could not keep its logits and nothing but its scan was enqueued - the caller runs the
+// forward as one launch per pass.
+static int forward_chunked(range_ctx* c, int64_t B, const ModelParams& m, const FwdChunkPlan& plan, double* out,
+                           range_stream_t stream, bool* chunked) {
+    *chunked = false;
+    ENTER_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_chunks = plan.tiles.size();
+    if (!c->ovl.aux_stream) {
+        // (a lower priority than the caller's stream was measured too: no difference, profiles/NOTES.md part S)
+        HIP_TRY(hipStreamCreateWithFlags(&c->ovl.aux_stream, hipStreamNonBlocking));
+    }
+    while (c->ovl.events.size() < n_chunks) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->ovl.events.push_back(e);
+    }
+    // the workspaces at their largest before anything is in flight: growing one synchronises the device
+    int64_t most_tiles = 0;
+    for (int t : plan.tiles) most_tiles = std::max<int64_t>(most_tiles, t);
+    HIP_TRY(c->pass.ws_stats_parts.ensure((size_t)plan.p1_splits * B * 4));
+    HIP_TRY(c->pass.ws_slabs.ensure((size_t)plan.p2_splits * std::min<int64_t>(B, most_tiles * QTILE) * VAL_DIM));
+    const float* ehat = c->pass.ws_ehat32.p;
+    const float* xq = c->pass.ws_xq.p;
+    float* stats = c->pass.ws_stats.p;
+    std::vector<int64_t> cuts{0};
+    for (int t : plan.tiles) cuts.push_back(std::min<int64_t>(B, cuts.back() + (int64_t)t * QTILE));
+    // chunk 0's pass 1
+    if (int rc = scan_stats_impl(c, ehat, xq, cuts[1], m.tau_sem, m.tau_geo, stats, 0, nullptr, nullptr, /*keep_logits=*/1, 0, B,
+                                 plan.p1_splits, stream))
+        return rc;
+    if (c->kept.kept_B != cuts[1]) return RANGE_OK;
+    *chunked = true;
+    HIP_TRY(hipEventRecord(c->ovl.events[0], s));
+    HIP_TRY(hipStreamWaitEvent(c->ovl.aux_stream, c->ovl.events[0], 0));
+    // (a call that fails half way still leaves the caller's stream behind the auxiliary work it enqueued)
+    size_t recorded = 0;
+    auto joined = [&](int rc) {
+        (void)hipStreamWaitEvent(s, c->ovl.events[recorded], 0);
+        return rc;
+    };
+    for (size_t i = 1; i < n_chunks; ++i) {
+        const int64_t q0 = cuts[i], nq = cuts[i + 1] - q0;
+        if (int rc = scan_stats_impl(c, ehat + q0 * KEY_DIM, xq + q0 * 4, nq, m.tau_sem, m.tau_geo, stats + q0 * 4, 0, nullptr, nullptr,
+                                     /*keep_logits=*/1, q0, B, plan.p1_splits, (range_stream_t)c->ovl.aux_stream, /*beside=*/true,
+                                     (size_t)plan.p1_splits * q0 * 4))
+            return joined(rc);
+        HIP_TRY(hipEventRecord(c->ovl.events[i], c->ovl.aux_stream));
+        recorded = i;
+    }
+    for (size_t i = 0; i < n_chunks; ++i) {
+        const int64_t q0 = cuts[i], nq = cuts[i + 1] - q0;
+        if (i > 0) HIP_TRY(hipStreamWaitEvent(s, c->ovl.events[i], 0));
+        SlabMap map{};
+        if (int rc = attend_impl(c, ehat + q0 * KEY_DIM, xq + q0 * 4, nq, m.tau_sem, m.tau_geo, m.beta, stats + q0 * 4, nullptr, &map, q0,
+                                 stream, nullptr, 0, plan.p2_splits))
+            return joined(rc);
+        HIP_TRY(launch_finalize(c->pass.ws_slabs.p, map, c->pass.ws_ehat64.p + q0 * KEY_DIM, nq, 0, nq, out + q0 * RANGE_OUT_DIM, s));
+    }
+    // (range_last_attend_geometry: the forward's, not its last chunk's)
+    c->pass.last_qtiles = (int)((B + QTILE - 1) / QTILE);
+    c->pass.last_splits = plan.p2_splits;
+    return RANGE_OK;
+}
+
 extern "C" {
 
 int range_forward(range_ctx* c, const double* lonlat, int64_t B, int32_t model, float beta,
@@ -95,6 +168,22 @@ int range_forward(range_ctx* c, const double* lonlat, int64_t B, int32_t model, 
     }
     // single GPU: the finalize kernel sums the split slabs itself (same fixed order as
     // reduce_parts_kernel, so the result is bit-identical to attend + finalize)
+    // a batch of several rounds of pass 2 against a bank beyond the stream-K walk, exact w @ V, the constant shift,
+    // logits kept: in chunks, pass 1 of the next chunk beside pass 2 (forward_chunked)
+    if (c->sw.allow_keep && c->bank.pv_mode == RANGE_PV_EXACT && c->bank.has_bank &&
+        plan_temperatures(m.tau_sem, m.tau_geo, B, false).shift == SHIFT_CONSTANT) {
+        const FwdChunkPlan plan = plan_forward_chunks(c->n_cu, plan_pass1(c->n_cu, c->bank.n_rows, B, false, 0, PLAN_CONSTS),
+                                                      plan_pass2(c->n_cu, c->bank.n_rows, B, c->sw.p2_streamk, PLAN_CONSTS),
+                                                      c->sw.fwd_overlap);
+        if (plan.tiles.size() >= 2) {
+            bool chunked = false;
+            if (int rc = forward_chunked(c, B, m, plan, out, stream, &chunked)) return rc;
+            if (chunked) {
+                c->pass.ws_queries = B;
+                return RANGE_OK;
+            }
+        }
+    }
     bool kept = false;
     SlabMap map{};
     if (int rc = scan_workspace(c, B, m, &kept, stream)) return rc;

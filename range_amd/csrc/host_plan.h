@@ -493,8 +493,10 @@ struct Pass2Plan {
     size_t slab_floats = 0;     // the slabs the launch writes
 };
 
-// allow_streamk: RANGE_P2_STREAMK, and the kernel of this call has the walk (the exact ones)
-inline Pass2Plan plan_pass2(int n_cu, int64_t n_rows, int64_t B, bool allow_streamk, const PlanConsts& K) {
+// allow_streamk: RANGE_P2_STREAMK, and the kernel of this call has the walk (the exact ones); force_splits > 0: the
+// caller's split count for the split scheme (a chunk of a forward takes the whole batch's: plan_forward_chunks)
+inline Pass2Plan plan_pass2(int n_cu, int64_t n_rows, int64_t B, bool allow_streamk, const PlanConsts& K,
+                            int force_splits = 0) {
     Pass2Plan p;
     p.n_blocks = (int32_t)((n_rows + K.blk - 1) / K.blk);
     p.n_qtiles = (int32_t)((B + K.qtile - 1) / K.qtile);
@@ -506,6 +508,7 @@ inline Pass2Plan plan_pass2(int n_cu, int64_t n_rows, int64_t B, bool allow_stre
     p.n_splits = choose_splits(p.n_qtiles, p.n_blocks, n_cu, 1,
                                std::max(32, std::min(512, (n_cu + p.n_qtiles - 1) / p.n_qtiles)),
                                std::max(0.001, 140.0 / (double)n_rows));
+    if (force_splits > 0) p.n_splits = std::max(1, std::min<int>(force_splits, std::max(1, p.n_blocks / 4)));
     // Stream-K (scan_common.h: SlabMap): as many workgroups as CUs, each with the same number of
     // (query tile, bank block) units (at least 4: tiny launches take fewer workgroups), one slab per
     // query tile a workgroup touches.  For banks and SHARDS of up to 50 000 rows - measured, 10 000
@@ -531,6 +534,66 @@ inline Pass2Plan plan_pass2(int n_cu, int64_t n_rows, int64_t B, bool allow_stre
         p.slab_floats = (size_t)p.n_splits * B * K.val_dim;
     }
     p.grid = p.streamk ? p.sk_groups : p.n_splits * p.n_qtiles;
+    return p;
+}
+
+// range_forward in chunks of query tiles (forward_host.h): pass 1 of chunk i + 1 runs on the CUs that pass 2 of
+// chunk i occupies (pass1_beside.h).  Every chunk takes the WHOLE batch's split counts of both passes (p1, p2: the
+// plans of all B queries): split boundaries depend on the bank's blocks and the split count only, the merge and
+// finalize orders on the split count only, so a chunked forward gives the bits of the single launches.
+struct FwdChunkPlan {
+    std::vector<int> tiles;             // query tiles of every chunk, in order; empty: no chunking
+    int p1_splits = 0, p2_splits = 0;
+};
+
+// overlap: RANGE_FWD_OVERLAP - 0 never, n > 0 chunks of n query tiles (tests), < 0 the rule:
+//   each chunk is a whole number of pass 2's rounds of n_cu workgroups, filled to FWD_CHUNK_FILL_PCT at least, and the
+//   chunks' rounds sum to the single launch's (no round is added);
+//   as many chunks as a near-equal division of the rounds allows (parts that differ by at most one round, the
+//   shorter ones first); the tiles a chunk could still take are missing in the first chunks: the smallest chunk
+//   comes first, its pass 1 is the exposed one.
+//   The benchmark - 256 CUs, 157 tiles x 13 splits = 2 041 workgroups in 8 rounds: 39 + 59 + 59 tiles
+//   (507, 767, 767 workgroups in 2, 3, 3 rounds).
+// No chunking for the stream-K walk of pass 2 (its workgroups are already one even round) and below two chunks.
+constexpr int FWD_CHUNK_FILL_PCT = 98;
+inline FwdChunkPlan plan_forward_chunks(int n_cu, const Pass1Plan& p1, const Pass2Plan& p2, int overlap) {
+    FwdChunkPlan p;
+    p.p1_splits = p1.n_splits;
+    p.p2_splits = p2.n_splits;
+    const int T = p2.n_qtiles, ns = p2.n_splits;
+    if (overlap == 0 || p2.streamk || T < 2 || ns < 1 || n_cu < 1) return p;
+    if (overlap > 0) {
+        for (int t0 = 0; t0 < T && overlap < T; t0 += overlap) p.tiles.push_back(std::min(overlap, T - t0));
+        return p;
+    }
+    const int64_t R = ((int64_t)T * ns + n_cu - 1) / n_cu;
+    for (int64_t C = std::min<int64_t>(R, T); C >= 2; --C) {
+        std::vector<int> lo((size_t)C), hi((size_t)C);
+        int64_t sum_lo = 0, sum_hi = 0;
+        bool ok = true;
+        for (int64_t i = 0; i < C && ok; ++i) {
+            const int64_t r = R / C + (i >= C - R % C ? 1 : 0);
+            // tiles whose workgroups make exactly r rounds: at most r n_cu of them, more than (r - 1) n_cu, and
+            // FWD_CHUNK_FILL_PCT of r n_cu
+            const int64_t most = r * n_cu / ns;
+            const int64_t fill = (FWD_CHUNK_FILL_PCT * r * n_cu + 100 * (int64_t)ns - 1) / (100 * (int64_t)ns);
+            const int64_t least = std::max<int64_t>(std::max<int64_t>(fill, (r - 1) * n_cu / ns + 1), 1);
+            ok = least <= most;
+            lo[(size_t)i] = (int)least;
+            hi[(size_t)i] = (int)most;
+            sum_lo += least;
+            sum_hi += most;
+        }
+        if (!ok || sum_lo > T || sum_hi < T) continue;
+        p.tiles = hi;
+        int64_t excess = sum_hi - T;
+        for (size_t i = 0; i < p.tiles.size() && excess > 0; ++i) {
+            const int64_t d = std::min<int64_t>(excess, hi[i] - lo[i]);
+            p.tiles[i] -= (int)d;
+            excess -= d;
+        }
+        return p;
+    }
     return p;
 }
 

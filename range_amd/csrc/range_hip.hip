@@ -23,6 +23,7 @@
 #include "pass1_sharp.h"
 #include "pass1_kept.h"
 #include "pass2.h"
+#include "pass1_beside.h"
 #include "topk_stream.h"
 #include "topk_gemm.h"
 #include "attend_bf16x3.h"

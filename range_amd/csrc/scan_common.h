@@ -125,15 +125,17 @@ __device__ __forceinline__ int64_t logit_tile(int64_t qtile, int32_t n_blocks, i
 // (b = 8j + x) take a CONTIGUOUS run of items: the workgroups resident on one XCD then stream the
 // same one or two splits and the bank rows are fetched once per XCD L2, not once per CU.
 // Bijective for any item count: XCD x owns cnt(x) = q + (x < r) items, total = 8q + r.
-__device__ __forceinline__ void decode_block(const ScanArgs& a, int& split, int& qt) {
+// decode_item: the same for block number b of a persistent launch's walk b = blockIdx, blockIdx + grid, ...
+// (a grid that is a multiple of 8 keeps b % 8, the XCD, along the walk).
+__device__ __forceinline__ void decode_item(const ScanArgs& a, int b, int& split, int& qt) {
     const int total = a.n_splits * a.n_qtiles;
-    const int b = blockIdx.x;
     const int x = b & 7, j = b >> 3;
     const int q = total >> 3, r = total & 7;
     const int item = x * q + (x < r ? x : r) + j;
     split = item / a.n_qtiles;
     qt = item - split * a.n_qtiles;
 }
+__device__ __forceinline__ void decode_block(const ScanArgs& a, int& split, int& qt) { decode_item(a, (int)blockIdx.x, split, qt); }
 
 struct QFrag {
     f32x4 q[16];   // B operand of S^T = K . Q^T: lane (j = query, g) holds Q[j][16s + 4g + 0..3]

@@ -77,10 +77,13 @@ static hipError_t launch_finalize(const float* slabs, const SlabMap& map, const 
 
 // first_query / total_queries / force_splits: range_scan_stats_at (a scan in chunks whose
 // kept logits share one workspace); a plain range_scan_stats is the chunk [0, B) of a scan of B.
+// beside / parts_offset (range_forward's later chunks, on a stream of their own): the persistent kernel that fits
+// next to pass 2 (pass1_beside.h), its statistics parts `parts_offset` floats into the workspace - a region of
+// the chunk's own, since the chunk before it may still be merging.
 static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32, int64_t B, float tau_sem,
                            float tau_geo, float* stats, int topk, float* topk_val, int64_t* topk_idx,
                            int32_t keep_logits, int64_t first_query, int64_t total_queries, int32_t force_splits,
-                           range_stream_t stream) {
+                           range_stream_t stream, bool beside = false, size_t parts_offset = 0) {
     if (!c || !ehat32 || !xq32 || !stats) return fail(RANGE_ERR_INVALID, "null argument");
     if (topk < 0 || topk > MAX_TOPK) return fail(RANGE_ERR_INVALID, "topk must be in [0,%d]", MAX_TOPK);
     if (topk > 0 && (!topk_val || !topk_idx)) return fail(RANGE_ERR_INVALID, "topk outputs null");
@@ -147,8 +150,8 @@ static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32,
         HIP_TRY(c->kept.ws_theta.ensure((size_t)B));
         a.rowmax = c->kept.ws_rowmax.p;
     }
-    HIP_TRY(c->pass.ws_stats_parts.ensure(p.part_floats));
-    a.out = c->pass.ws_stats_parts.p;
+    HIP_TRY(c->pass.ws_stats_parts.ensure(parts_offset + p.part_floats));
+    a.out = c->pass.ws_stats_parts.p + parts_offset;
     if (topk_scan) {
         HIP_TRY(c->topk.ws_cand_val.ensure(p.part_floats * MAX_TOPK));
         HIP_TRY(c->topk.ws_cand_idx.ensure(p.part_floats * MAX_TOPK));
@@ -161,17 +164,25 @@ static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32,
                                                         {scan_stats_kernel<false, true>, scan_stats_kernel<false, false>}};
     // pass 1 with a running maximum (pass1_sharp.h) [0: with the geographic head, 1: without]
     static void (*const sharp_kernels[2])(ScanArgs) = {sharp_scan_stats_kernel<true>, sharp_scan_stats_kernel<false>};
+    // pass 1 beside pass 2 (pass1_beside.h): one persistent workgroup per CU [0: with the geographic head, 1: without]
+    static void (*const beside_kernels[2])(ScanArgs) = {scan_stats_beside_kernel<true>, scan_stats_beside_kernel<false>};
+    if (beside && (topk > 0 || route.shift == SHIFT_RUNNING_MAX))
+        return fail(RANGE_ERR_INVALID, "internal: pass 1 beside pass 2 has the constant shift and no top-k");
     {
         ProfScope ps(c, RANGE_PROF_SCAN_STATS, s);
-        void (*const kernel)(ScanArgs) = route.shift == SHIFT_RUNNING_MAX ? sharp_kernels[!geo] : scan_kernels[!geo][!topk_scan];
-        if (int lrc = launch(kernel, dim3((unsigned)p.grid), dim3(256), SCAN_LDS_BYTES, s, a)) return lrc;
+        if (beside) {
+            if (int lrc = launch(beside_kernels[!geo], dim3((unsigned)std::min(c->n_cu, p.grid)), dim3(256), BESIDE_LDS_BYTES, s, a)) return lrc;
+        } else {
+            void (*const kernel)(ScanArgs) = route.shift == SHIFT_RUNNING_MAX ? sharp_kernels[!geo] : scan_kernels[!geo][!topk_scan];
+            if (int lrc = launch(kernel, dim3((unsigned)p.grid), dim3(256), SCAN_LDS_BYTES, s, a)) return lrc;
+        }
     }
     if (a.logits && keep_logits) {
         c->kept.kept_B = first_query + B;
         c->kept.kept_total = total_queries;
         c->kept.kept_blocks = a.n_blocks;
     }
-    rc = launch_merge_stats(p.merge_by_wave, c->pass.ws_stats_parts.p, a.n_splits, B, stats, s);
+    rc = launch_merge_stats(p.merge_by_wave, a.out, a.n_splits, B, stats, s);
     if (rc) return rc;
     int n_parts = a.n_splits, per_part = 4 * MAX_TOPK;     // the in-scan lists
     if (topk_from_kept) {
@@ -198,11 +209,12 @@ static int scan_stats_impl(range_ctx* c, const float* ehat32, const float* xq32,
 // kept_first >= 0: queries [kept_first, kept_first + B) of the last scan whose logits were kept
 // (attend_stored_kernel; ehat32 is not read); kept_first < 0: recompute the logits.
 // diag_dev non-null (range_attend_diag): the instrumented build of the recomputing kernel, always in
-// the split scheme, with the slabs as its only output.
+// the split scheme, with the slabs as its only output.  force_splits > 0: the split scheme's split count
+// (range_forward's chunks take the whole batch's).
 static int attend_impl(range_ctx* c, const float* ehat32, const float* xq32, int64_t B, float tau_sem,
                        float tau_geo, float beta, const float* stats_global, float* partial,
                        SlabMap* map_out, int64_t kept_first, range_stream_t stream,
-                       unsigned long long* diag_dev = nullptr, int64_t diag_capacity = 0) {
+                       unsigned long long* diag_dev = nullptr, int64_t diag_capacity = 0, int32_t force_splits = 0) {
     if (!c || (!ehat32 && kept_first < 0) || !xq32 || !stats_global)
         return fail(RANGE_ERR_INVALID, "null argument");
     if (kept_first >= 0) {
@@ -223,7 +235,7 @@ static int attend_impl(range_ctx* c, const float* ehat32, const float* xq32, int
     if (bf16x3 && plan_temperatures(tau_sem, tau_geo, B, false).shift == SHIFT_RUNNING_MAX)
         return fail(RANGE_ERR_INVALID, "pv mode bf16x3 is not supported at temperatures above %g", (double)RANGE_MAX_TAU);
     // (stream-K: the exact kernels only)
-    const Pass2Plan p = plan_pass2(c->n_cu, c->bank.n_rows, B, c->sw.p2_streamk && !bf16x3 && !diag_dev, PLAN_CONSTS);
+    const Pass2Plan p = plan_pass2(c->n_cu, c->bank.n_rows, B, c->sw.p2_streamk && !bf16x3 && !diag_dev, PLAN_CONSTS, force_splits);
     a.n_blocks = p.n_blocks;
     a.n_qtiles = p.n_qtiles;
     a.n_splits = p.n_splits;
