@@ -19,8 +19,14 @@ SYMBOLS = (
     "range_neighbor_select", "range_neighbor_select_grid", "range_neighbor_rank", "range_neighbor_rank_grid",
     "range_neighbor_prior", "range_neighbor_prior_grid",
 )
+#: the KDE prior's entry points in the same header
+KDE_SYMBOLS = (
+    "range_kde_plan", "range_set_kde_points", "range_kde_scale_bits", "range_kde_rank", "range_kde_rank_grid",
+    "range_kde_prior", "range_kde_prior_grid",
+)
 RADIUS, KNN, CELL = 0, 1, 2
 MAX_CLASSES = 32768
+KDE_MAX_CLASSES = 16384
 CELL_UNIFORM, CELL_OUTSIDE = -1, -2      # a query that takes the uniform prior; a training point that never votes
 
 _bound = False
@@ -45,7 +51,16 @@ def load_library() -> C.CDLL:
     lib.range_neighbor_rank_grid.argtypes = [vp, vp, vp, i64] + pred + [vp, i32, vp, vp, vp, vp, i64, i32, vp]
     lib.range_neighbor_prior.argtypes = [vp, vp, vp, i64] + pred + [vp, vp]
     lib.range_neighbor_prior_grid.argtypes = [vp, vp, vp, i64] + pred + [vp, vp, i64, i32, vp]
-    for name in SYMBOLS:
+    kde = [vp, vp, vp, vp, i64]                         # ctx, q, thr, two_h2, B
+    lib.range_kde_plan.argtypes = [i64, i64, i32, i64, i64, i32, vp]
+    lib.range_set_kde_points.argtypes = [vp, vp, vp, vp, i64, i32, i32]
+    lib.range_kde_scale_bits.argtypes = [vp]
+    lib.range_kde_scale_bits.restype = i32
+    lib.range_kde_rank.argtypes = kde + [vp, i32, vp, vp, vp, vp, vp]
+    lib.range_kde_rank_grid.argtypes = kde + [vp, i32, vp, vp, vp, vp, i64, i32, vp]
+    lib.range_kde_prior.argtypes = kde + [vp, vp]
+    lib.range_kde_prior_grid.argtypes = kde + [vp, vp, i64, i32, vp]
+    for name in SYMBOLS + KDE_SYMBOLS:
         getattr(lib, name)
     _bound = True
     return lib
@@ -57,6 +72,15 @@ def plan(B: int, N: int, num_classes: int, k: int = 0, max_grid: int = 0, chunks
     out = np.zeros(8, dtype=np.int64)
     _check(lib, lib.range_neighbor_plan(B, N, num_classes, k, max_grid, chunks, out.ctypes.data))
     keys = ("group", "groups", "grid", "chunks", "lds_bytes", "ws_bytes", "digit_bits", "passes")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def kde_plan(B: int, M: int, num_classes: int, total_count: int, max_grid: int = 0, chunks: int = 0) -> Dict[str, int]:
+    """The KDE prior's launch plan (host_plan.h: kde_plan); needs no GPU."""
+    lib = load_library()
+    out = np.zeros(8, dtype=np.int64)
+    _check(lib, lib.range_kde_plan(B, M, num_classes, total_count, max_grid, chunks, out.ctypes.data))
+    keys = ("group", "groups", "grid", "chunks", "lds_bytes", "ws_bytes", "scale_bits", "tiles")
     return dict(zip(keys, (int(v) for v in out)))
 
 
@@ -152,3 +176,72 @@ class NeighborEngine(HipEngine):
                 self._h, _ptr(q), _ptr(qcell), B, mode, int(k), float(thr), float(pc), float(cpc), prior.data_ptr(),
                 _ptr(counts), int(max_grid), int(chunks), self._stream()))
         return (prior, counts) if want_counts else prior
+
+    # ---- the KDE prior (a weighted set in the same slot)
+
+    def set_kde_points(self, lonlat: np.ndarray, classes: np.ndarray, counts: np.ndarray, num_classes: int,
+                       haversine: bool) -> None:
+        """``lonlat`` (M, 2) float64 (lon, lat) of the bins - radians with ``haversine``, else degrees -, ``classes``
+        (M,) in ``[0, num_classes)``, ``counts`` (M,) >= 1: host arrays (range_set_kde_points)."""
+        ll = np.ascontiguousarray(lonlat, dtype=np.float64)
+        cls = np.ascontiguousarray(classes, dtype=np.int32)
+        cnt64 = np.asarray(counts, dtype=np.int64)
+        if ll.ndim != 2 or ll.shape[1] != 2 or cls.shape != (ll.shape[0],) or cnt64.shape != cls.shape:
+            raise ValueError(f"lonlat (M, 2), classes (M,) and counts (M,), got {ll.shape}, {cls.shape} and {cnt64.shape}")
+        if cnt64.size and (cnt64.max() > 2 ** 31 - 1 or cnt64.min() < -2 ** 31):
+            raise ValueError("a count beyond int32")
+        cnt = np.ascontiguousarray(cnt64, dtype=np.int32)
+        _check(self.lib, self.lib.range_set_kde_points(self._h, ll.ctypes.data, cls.ctypes.data, cnt.ctypes.data, ll.shape[0],
+                                                       int(num_classes), int(bool(haversine))))
+        self.haversine = bool(haversine)
+
+    @property
+    def kde_scale_bits(self) -> int:
+        return int(self.lib.range_kde_scale_bits(self._h))
+
+    def _kde_inputs(self, q: torch.Tensor, thr: torch.Tensor, two_h2: torch.Tensor) -> int:
+        self._t(q, torch.float64, (2,))
+        B = q.shape[0]
+        for t in (thr, two_h2):
+            self._t(t, torch.float64, ())
+            if t.shape[0] != B:
+                raise ValueError(f"{t.shape[0]} thresholds / bandwidths for {B} rows")
+        return B
+
+    def kde_rank(self, q: torch.Tensor, thr: torch.Tensor, two_h2: torch.Tensor, labels: torch.Tensor,
+                 img: Optional[torch.Tensor] = None, max_grid: int = 0, chunks: int = 0):
+        """(``greater``, ``tied_after``, ``argmax``), (B,) int32 each, over ``img.double() * prior``
+        (range_kde_rank_grid)."""
+        B = self._kde_inputs(q, thr, two_h2)
+        C_ = self.neighbor_classes
+        self._t(labels, torch.int32, ())
+        if labels.shape[0] != B:
+            raise ValueError(f"{labels.shape[0]} labels for {B} rows")
+        kind = CSP_IMG_NONE
+        if img is not None:
+            if img.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"image predictions must be float32 or float64, got {img.dtype}")
+            self._t(img, img.dtype, (C_,))
+            if img.shape[0] != B:
+                raise ValueError(f"{img.shape[0]} rows of image predictions for {B} rows")
+            kind = CSP_IMG_F32 if img.dtype == torch.float32 else CSP_IMG_F64
+        out = tuple(self._empty((B,), torch.int32) for _ in range(3))
+        if B:
+            _check(self.lib, self.lib.range_kde_rank_grid(
+                self._h, q.data_ptr(), thr.data_ptr(), two_h2.data_ptr(), B, _ptr(img), kind, labels.data_ptr(),
+                out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), int(max_grid), int(chunks), self._stream()))
+        return out
+
+    def kde_prior(self, q: torch.Tensor, thr: torch.Tensor, two_h2: torch.Tensor, want_sums: bool = False,
+                  max_grid: int = 0, chunks: int = 0):
+        """The (B, num_classes) float64 priors (range_kde_prior_grid); with ``want_sums`` also the fixed-point sums,
+        (B, num_classes) int64 holding the kernel's uint64 (below 2^62)."""
+        B = self._kde_inputs(q, thr, two_h2)
+        C_ = self.neighbor_classes
+        prior = self._empty((B, C_), torch.float64)
+        sums = self._empty((B, C_), torch.int64) if want_sums else None
+        if B:
+            _check(self.lib, self.lib.range_kde_prior_grid(
+                self._h, q.data_ptr(), thr.data_ptr(), two_h2.data_ptr(), B, prior.data_ptr(), _ptr(sums), int(max_grid),
+                int(chunks), self._stream()))
+        return (prior, sums) if want_sums else prior

@@ -14,9 +14,9 @@ NaN if there is one.  A row whose label's score is NaN has no rank: 0 here, pred
 
 numpy only: importable, and testable, without a GPU.  ``compute_acc_batch`` with a CSP prior runs
 ``CspLocationModel.label_ranks`` - one kernel launch per chunk, three integers per sample, no (B, num_classes)
-matrix.  The location-only baselines ``'train_freq'``, ``'nn_dist'``, ``'nn_knn'`` and ``'grid'`` take the
-objects of ``range_amd.geo_baselines`` as ``prior`` (a (C,) array for ``'train_freq'``); as in the reference they
-keep every row - a NaN location has the uniform prior."""
+matrix.  The location-only baselines ``'train_freq'``, ``'nn_dist'``, ``'nn_knn'``, ``'grid'`` and ``'kde'`` take
+the objects of ``range_amd.geo_baselines`` as ``prior`` (a (C,) array for ``'train_freq'``); as in the reference
+they keep every row - a NaN location has the uniform prior."""
 from __future__ import annotations
 
 import logging
@@ -25,10 +25,11 @@ from typing import List, Tuple
 import numpy as np
 
 TOP_KS = (1, 3, 5, 10)
-#: prior types of eval_helper.py this module does not serve
+#: prior types of eval_helper.py that have no path without a prior object: 'kde' needs a geo_baselines.KdePrior,
+#: 'tang_et_al' a trained network that is not in the tree (it is not served at all)
 UNSUPPORTED_PRIORS = ("kde", "tang_et_al")
 #: the location-only baselines (range_amd/geo_baselines.py) and what ``prior`` is for each
-BASELINE_PRIORS = ("train_freq", "nn_dist", "nn_knn", "grid")
+BASELINE_PRIORS = ("train_freq", "nn_dist", "nn_knn", "grid", "kde")
 _NEIGHBOR_PTYPE = {"nn_dist": "distance", "nn_knn": "knn"}
 
 
@@ -81,8 +82,9 @@ def compute_acc_batch(val_preds, val_classes, val_split, val_feats=None, train_c
     loaded with ``class_head=True`` and ``prior_type`` its ``spa_enc_type`` or ``'geo_net'`` ranks ``val_preds *
     prior(val_feats)``, ``batch_size`` rows a call; ``'train_freq'`` with ``prior`` the (num_classes,) array of
     ``geo_baselines.train_freq_prior`` ranks ``val_preds * prior`` on the host; ``'nn_dist'`` / ``'nn_knn'`` with
-    ``prior`` a ``geo_baselines.NeighborPrior`` and ``'grid'`` with a ``geo_baselines.GridPrior`` rank ``val_preds *
-    prior(val_feats)`` on the GPU and drop no row; any other ``prior_type`` raises NotImplementedError.  Logs the
+    ``prior`` a ``geo_baselines.NeighborPrior``, ``'grid'`` with a ``geo_baselines.GridPrior`` and ``'kde'`` with a
+    ``geo_baselines.KdePrior`` rank ``val_preds * prior(val_feats)`` on the GPU and drop no row; any other
+    ``prior_type``, or one of these without its object, raises NotImplementedError.  Logs the
     reference's ``Top k acc (%)`` lines per split with its denominators (a sample the reference drops - no
     location - is a miss over the whole split) and returns its list of predicted classes, of the samples it keeps;
     with ``return_acc=True`` also ``{split: {k: accuracy in per cent}}``."""
@@ -129,7 +131,7 @@ def compute_acc_batch(val_preds, val_classes, val_split, val_feats=None, train_c
             ranks[sl][ok] = 1 + g[ok].astype(np.int64) + e[ok]
             pred[sl] = np.argmax(blk, axis=1)
         kept = np.ones(N, dtype=bool)
-    elif prior_type in ("nn_dist", "nn_knn", "grid") and prior is not None and hasattr(prior, "label_ranks"):
+    elif prior_type in ("nn_dist", "nn_knn", "grid", "kde") and prior is not None and hasattr(prior, "label_ranks"):
         if val_feats is None:
             raise ValueError(f"prior_type={prior_type!r} needs val_feats, the (lon, lat) degrees")
         extra = {"ptype": _NEIGHBOR_PTYPE[prior_type]} if prior_type in _NEIGHBOR_PTYPE else {}
@@ -143,7 +145,7 @@ def compute_acc_batch(val_preds, val_classes, val_split, val_feats=None, train_c
     else:
         raise NotImplementedError(f"compute_acc_batch: prior_type={prior_type!r} is not implemented (only 'no_prior', a CSP "
                                   "prior - 'geo_net' or the model's spa_enc_type with prior a CspLocationModel - and the "
-                                  "baselines 'train_freq', 'nn_dist', 'nn_knn', 'grid' with their prior objects)")
+                                  "baselines 'train_freq', 'nn_dist', 'nn_knn', 'grid', 'kde' with their prior objects)")
     logger.info(val_classes[kept].shape)
     acc = {}
     for ii, split in enumerate(np.unique(val_split)):

@@ -137,13 +137,16 @@ struct range_ctx {
         DevBuf<int64_t> ws_idx;
     } checker;
     // range_set_neighbors: the packed training set of the neighbour / grid geo priors (neighbor_kernel.h), the
-    // chunks' partial count rows of a split scan, the selection of a k-nearest-neighbour call
+    // chunks' partial count rows of a split scan, the selection of a k-nearest-neighbour call.  range_set_kde_points
+    // installs a WEIGHTED set in the same slot (kde_kernel.h): the bins, their counts in the points' cell word
     struct Neighbors {
         int64_t N = 0;                   // 0: no set installed
         int C = 0;
         bool hav = false, has_cells = false;
+        int kde_bits = 0;                // > 0: a weighted set, the scale bits of its fixed-point sums
         DevBuf<NeighborPoint> d_pts;
         DevBuf<int32_t> ws_counts;
+        DevBuf<uint64_t> ws_sums;        // a split KDE scan's partial rows
         DevBuf<double> ws_redk;
         DevBuf<int64_t> ws_jlast;
     } nb;

@@ -1153,6 +1153,28 @@ inline int neighbor_group(int C) {
     return (int)std::min<size_t>(NEIGHBOR_MAX_GROUP, NEIGHBOR_COUNT_LDS / ((size_t)C * 4));
 }
 
+// the geometry of a vote scan whose LDS rows have `entry`-byte entries and G = `group` rows a workgroup: groups,
+// tiles, grids, chunks, LDS and workspace (ws_ints counts entries).  The arguments have been checked.
+inline void neighbor_plan_rows(NeighborPlan& p, int64_t B, int64_t N, int C, int64_t max_grid, int chunks, size_t entry, int group) {
+    const int64_t cap = max_grid > 0 ? std::min(max_grid, NEIGHBOR_MAX_GRID) : NEIGHBOR_MAX_GRID;
+    p.group = group;
+    p.groups = (B + p.group - 1) / p.group;
+    p.n_tiles = (N + NEIGHBOR_BLOCK - 1) / NEIGHBOR_BLOCK;
+    p.grid = (unsigned)std::min(p.groups, cap);
+    const size_t row_ints = (size_t)p.groups * (size_t)p.group * (size_t)C;       // of one chunk
+    const int64_t want = chunks > 0 ? (int64_t)chunks : (NEIGHBOR_TARGET_WG + p.groups - 1) / p.groups;
+    const int64_t fits = std::max<int64_t>(1, (int64_t)(NEIGHBOR_MAX_WS / entry / row_ints));
+    p.chunks = (int)std::min(std::min(std::min(want, p.n_tiles), std::min(fits, cap)), (int64_t)NEIGHBOR_MAX_CHUNKS);
+    p.lds_bytes = (((size_t)p.group * (size_t)C * entry + 15) & ~(size_t)15) + (size_t)p.group * NEIGHBOR_QUERY_LDS;
+    if (p.chunks > 1) {
+        p.ws_ints = (size_t)p.chunks * row_ints;
+        p.ws_bytes = p.ws_ints * entry;
+        p.fold_grid = (unsigned)std::min(p.groups, cap);
+    }
+    p.select_grid = (unsigned)std::min(B, cap);
+    p.select_lds = (size_t)(NEIGHBOR_BINS + NEIGHBOR_BLOCK + 16) * 4;
+}
+
 // B queries, N training points, C classes; k: neighbours of the selection (0: none asked for).  max_grid: 0 the
 // plan's choice, g > 0 at most g workgroups a launch and grid dimension.  chunks: 0 the plan's choice, n > 0 at
 // most n chunks (never more than the tiles, NEIGHBOR_MAX_CHUNKS or what the workspace cap allows).
@@ -1163,23 +1185,47 @@ inline NeighborPlan neighbor_plan(int64_t B, int64_t N, int C, int64_t k, int64_
     if (C < 1 || C > NEIGHBOR_MAX_CLASSES) { p.why = "num_classes outside 1 .. 32768 (one count row of LDS)"; return p; }
     if (k < 0 || k > N) { p.why = "k outside 1 .. N"; return p; }
     if (max_grid < 0 || chunks < 0) { p.why = "max_grid or chunks below 0"; return p; }
-    const int64_t cap = max_grid > 0 ? std::min(max_grid, NEIGHBOR_MAX_GRID) : NEIGHBOR_MAX_GRID;
-    p.group = neighbor_group(C);
-    p.groups = (B + p.group - 1) / p.group;
-    p.n_tiles = (N + NEIGHBOR_BLOCK - 1) / NEIGHBOR_BLOCK;
-    p.grid = (unsigned)std::min(p.groups, cap);
-    const size_t row_ints = (size_t)p.groups * (size_t)p.group * (size_t)C;       // of one chunk
-    const int64_t want = chunks > 0 ? (int64_t)chunks : (NEIGHBOR_TARGET_WG + p.groups - 1) / p.groups;
-    const int64_t fits = std::max<int64_t>(1, (int64_t)(NEIGHBOR_MAX_WS / 4 / row_ints));
-    p.chunks = (int)std::min(std::min(std::min(want, p.n_tiles), std::min(fits, cap)), (int64_t)NEIGHBOR_MAX_CHUNKS);
-    p.lds_bytes = (((size_t)p.group * (size_t)C * 4 + 15) & ~(size_t)15) + (size_t)p.group * NEIGHBOR_QUERY_LDS;
-    if (p.chunks > 1) {
-        p.ws_ints = (size_t)p.chunks * row_ints;
-        p.ws_bytes = p.ws_ints * 4;
-        p.fold_grid = (unsigned)std::min(p.groups, cap);
-    }
-    p.select_grid = (unsigned)std::min(B, cap);
-    p.select_lds = (size_t)(NEIGHBOR_BINS + NEIGHBOR_BLOCK + 16) * 4;
+    neighbor_plan_rows(p, B, N, C, max_grid, chunks, 4, neighbor_group(C));
+    p.valid = true;
+    return p;
+}
+
+// The KDE geo prior (kde_kernel.h): the vote scan's geometry over M bins with uint64 rows - the fixed-point sums of
+// the members' weights - so G is half the neighbour priors' (2 at C = 8142, 1 at the class cap KDE_MAX_CLASSES =
+// 16384, a row of 128 KB).  A weight w in [0, 1] enters a row as count * rint(w * 2^scale_bits); scale_bits is the
+// largest s <= KDE_MAX_SCALE_BITS with total_count * 2^s < 2^62, total_count the sum of the bins' counts (at most
+// 2^31 - 1), so that no row - nor the sum of a query's rows - can reach 2^62.
+constexpr int KDE_MAX_CLASSES = 16384;
+constexpr int KDE_MAX_SCALE_BITS = 52;
+constexpr int64_t KDE_MAX_TOTAL = (INT64_C(1) << 31) - 1;
+
+struct KdePlan : NeighborPlan {
+    int scale_bits = 0;
+};
+
+inline int kde_group(int C) {
+    if (C < 1 || C > KDE_MAX_CLASSES) return 0;
+    return (int)std::min<size_t>(NEIGHBOR_MAX_GROUP, NEIGHBOR_COUNT_LDS / ((size_t)C * 8));
+}
+
+// (0: total_count outside 1 .. KDE_MAX_TOTAL)
+inline int kde_scale_bits(int64_t total_count) {
+    if (total_count < 1 || total_count > KDE_MAX_TOTAL) return 0;
+    int bits = 0;                        // total_count < 2^bits
+    while ((INT64_C(1) << bits) <= total_count) ++bits;
+    return std::min(KDE_MAX_SCALE_BITS, 62 - bits);
+}
+
+// B queries, M bins, C classes, total_count the sum of the bins' counts; max_grid and chunks as neighbor_plan's
+inline KdePlan kde_plan(int64_t B, int64_t M, int C, int64_t total_count, int64_t max_grid = 0, int chunks = 0) {
+    KdePlan p;
+    if (B < 1 || B > NEIGHBOR_MAX_QUERIES) { p.why = "B outside 1 .. 2^31 - 1"; return p; }
+    if (M < 1 || M > NEIGHBOR_MAX_POINTS) { p.why = "M outside 1 .. 2^31 - 1"; return p; }
+    if (C < 1 || C > KDE_MAX_CLASSES) { p.why = "num_classes outside 1 .. 16384 (one row of 64-bit sums in LDS)"; return p; }
+    if (total_count < M || total_count > KDE_MAX_TOTAL) { p.why = "total count outside M .. 2^31 - 1"; return p; }
+    if (max_grid < 0 || chunks < 0) { p.why = "max_grid or chunks below 0"; return p; }
+    neighbor_plan_rows(p, B, M, C, max_grid, chunks, 8, kde_group(C));
+    p.scale_bits = kde_scale_bits(total_count);
     p.valid = true;
     return p;
 }

@@ -21,6 +21,47 @@ static int need_neighbors(const range_ctx* c) {
     return c->nb.N ? RANGE_OK : fail(RANGE_ERR_STATE, "no training set installed (range_set_neighbors)");
 }
 
+// the classes of a set to install: RANGE_ERR_INVALID names the first outside [0, C)
+static int neighbor_check_classes(const int32_t* classes, int64_t N, int32_t C) {
+    for (int64_t j = 0; j < N; ++j)
+        if (classes[j] < 0 || classes[j] >= C)
+            return fail(RANGE_ERR_INVALID, "class %d of training point %lld outside 0 .. %d", classes[j], (long long)j, C - 1);
+    return RANGE_OK;
+}
+
+// packs N checked points into the context's slot; `extra` (N) int32 or null fills the point's free word: the grid
+// cells of range_set_neighbors, or - kde_bits > 0, a weighted set (kde_host.h) - the bins' counts
+static int neighbor_install(range_ctx* c, const double* lonlat, const int32_t* classes, const int32_t* extra, int64_t N, int32_t C,
+                            int32_t haversine, int kde_bits) {
+    ENTER_DEVICE(c);
+    HIP_TRY(hipDeviceSynchronize());         // a launch in flight may still read the set this call replaces
+    range_ctx::Neighbors& m = c->nb;
+    m.N = 0;
+    DevBuf<double> d_ll;
+    DevBuf<int32_t> d_cls, d_cell;
+    HIP_TRY(d_ll.ensure((size_t)N * 2));
+    HIP_TRY(d_cls.ensure((size_t)N));
+    HIP_TRY(hipMemcpy(d_ll.p, lonlat, (size_t)N * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_cls.p, classes, (size_t)N * 4, hipMemcpyHostToDevice));
+    if (extra) {
+        HIP_TRY(d_cell.ensure((size_t)N));
+        HIP_TRY(hipMemcpy(d_cell.p, extra, (size_t)N * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(m.d_pts.ensure((size_t)N));
+    const int64_t n_tiles = (N + NEIGHBOR_BLOCK - 1) / NEIGHBOR_BLOCK;
+    const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, NEIGHBOR_MAX_GRID);
+    if (int rc = launch(neighbor_prep_kernel, dim3(grid), dim3(NEIGHBOR_BLOCK), 0, (hipStream_t) nullptr, (const double*)d_ll.p,
+                        (const int32_t*)d_cls.p, (const int32_t*)d_cell.p, N, (int32_t)(haversine != 0), m.d_pts.p))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    m.C = C;
+    m.hav = haversine != 0;
+    m.has_cells = extra != nullptr && kde_bits == 0;
+    m.kde_bits = kde_bits;
+    m.N = N;
+    return RANGE_OK;
+}
+
 static int neighbor_select_impl(range_ctx* c, const double* q, int64_t B, int64_t k, double* red_k, int64_t* j_last,
                                 int64_t max_grid, hipStream_t s) {
     if (k < 1 || k > c->nb.N)
@@ -126,34 +167,8 @@ int range_set_neighbors(range_ctx* c, const double* lonlat, const int32_t* class
     if (!c || !lonlat || !classes) return fail(RANGE_ERR_INVALID, "null argument");
     const NeighborPlan p = neighbor_plan(1, N, C, 0);
     if (!p.valid) return fail(RANGE_ERR_INVALID, "N = %lld, C = %d: %s", (long long)N, C, p.why);
-    for (int64_t j = 0; j < N; ++j)
-        if (classes[j] < 0 || classes[j] >= C)
-            return fail(RANGE_ERR_INVALID, "class %d of training point %lld outside 0 .. %d", classes[j], (long long)j, C - 1);
-    ENTER_DEVICE(c);
-    HIP_TRY(hipDeviceSynchronize());         // a launch in flight may still read the set this call replaces
-    range_ctx::Neighbors& m = c->nb;
-    m.N = 0;
-    DevBuf<double> d_ll;
-    DevBuf<int32_t> d_cls, d_cell;
-    HIP_TRY(d_ll.ensure((size_t)N * 2));
-    HIP_TRY(d_cls.ensure((size_t)N));
-    HIP_TRY(hipMemcpy(d_ll.p, lonlat, (size_t)N * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_cls.p, classes, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (cells) {
-        HIP_TRY(d_cell.ensure((size_t)N));
-        HIP_TRY(hipMemcpy(d_cell.p, cells, (size_t)N * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(m.d_pts.ensure((size_t)N));
-    const unsigned grid = (unsigned)std::min<int64_t>(p.n_tiles, NEIGHBOR_MAX_GRID);
-    if (int rc = launch(neighbor_prep_kernel, dim3(grid), dim3(NEIGHBOR_BLOCK), 0, (hipStream_t) nullptr, (const double*)d_ll.p,
-                        (const int32_t*)d_cls.p, (const int32_t*)d_cell.p, N, (int32_t)(haversine != 0), m.d_pts.p))
-        return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    m.C = C;
-    m.hav = haversine != 0;
-    m.has_cells = cells != nullptr;
-    m.N = N;
-    return RANGE_OK;
+    if (int rc = neighbor_check_classes(classes, N, C)) return rc;
+    return neighbor_install(c, lonlat, classes, cells, N, C, haversine, 0);
 }
 
 int64_t range_neighbor_points(const range_ctx* c) { return c ? c->nb.N : 0; }

@@ -181,6 +181,45 @@ __device__ __forceinline__ bool neighbor_member(const NeighborQuery& q, const Ne
     return red < rk || (red == rk && j <= q.j_last);
 }
 
+// the three integers of row b by one wave: the scores are img[b, c] * prior_at(c) (prior_at(c) without image
+// predictions), the rule csp_rank_kernel.h's.  Shared by the count priors here and the KDE prior (kde_kernel.h).
+template <class PriorAt>
+__device__ __forceinline__ void neighbor_rank_row(const void* img, int32_t img_kind, const int32_t* labels, int32_t* greater,
+                                                  int32_t* tied, int32_t* argmax, int64_t b, int C, int lane, const PriorAt& prior_at) {
+#pragma clang fp contract(off)
+    const auto score_of = [&](int c) {
+        const double p = prior_at(c);
+        if (img_kind == CSP_IMG_F32) return (double)static_cast<const float*>(img)[b * C + c] * p;
+        if (img_kind == CSP_IMG_F64) return static_cast<const double*>(img)[b * C + c] * p;
+        return p;
+    };
+    const int32_t label = labels[b];
+    const bool bad = label < 0 || label >= C;
+    const double st = bad ? 0.0 : score_of(label);
+    int32_t ngt = 0, ntie = 0, bi = CSP_RANK_NO_INDEX;
+    double bs = -__builtin_inf();
+    for (int c = lane; c < C; c += 64) {
+        const double s = score_of(c);
+        ngt += (c != label && !(s <= st)) ? 1 : 0;
+        ntie += (s == st && c > label) ? 1 : 0;
+        if (csp_rank_before(s, c, bs, bi)) { bs = s; bi = c; }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        ngt += __shfl_xor(ngt, o);
+        ntie += __shfl_xor(ntie, o);
+        const double os = __shfl_xor(bs, o);
+        const int32_t oi = __shfl_xor(bi, o);
+        if (csp_rank_before(os, oi, bs, bi)) { bs = os; bi = oi; }
+    }
+    if (lane == 0) {
+        const int32_t flag = bad ? CSP_RANK_BAD_LABEL : st != st ? CSP_RANK_NAN : 0;
+        greater[b] = flag ? flag : ngt;
+        tied[b] = flag ? flag : ntie;
+        argmax[b] = flag ? flag : bi;
+    }
+}
+
 // the rows of a group, a wave each (rows wave, wave + 16, ...): counts / priors on request, the three integers
 template <int MODE>
 __device__ __forceinline__ void neighbor_rank_group(const NeighborArgs& a, const int32_t* counts, const NeighborQuery* qs,
@@ -209,37 +248,7 @@ __device__ __forceinline__ void neighbor_rank_group(const NeighborArgs& a, const
         if (a.prior)
             for (int c = lane; c < C; c += 64) a.prior[b * C + c] = prior_of(row[c]);
         if (!a.greater) continue;
-        const auto score_of = [&](int c) {
-            const double p = prior_of(row[c]);
-            if (a.img_kind == CSP_IMG_F32) return (double)static_cast<const float*>(a.img)[b * C + c] * p;
-            if (a.img_kind == CSP_IMG_F64) return static_cast<const double*>(a.img)[b * C + c] * p;
-            return p;
-        };
-        const int32_t label = a.labels[b];
-        const bool bad = label < 0 || label >= C;
-        const double st = bad ? 0.0 : score_of(label);
-        int32_t ngt = 0, ntie = 0, bi = CSP_RANK_NO_INDEX;
-        double bs = -__builtin_inf();
-        for (int c = lane; c < C; c += 64) {
-            const double s = score_of(c);
-            ngt += (c != label && !(s <= st)) ? 1 : 0;
-            ntie += (s == st && c > label) ? 1 : 0;
-            if (csp_rank_before(s, c, bs, bi)) { bs = s; bi = c; }
-        }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            ngt += __shfl_xor(ngt, o);
-            ntie += __shfl_xor(ntie, o);
-            const double os = __shfl_xor(bs, o);
-            const int32_t oi = __shfl_xor(bi, o);
-            if (csp_rank_before(os, oi, bs, bi)) { bs = os; bi = oi; }
-        }
-        if (lane == 0) {
-            const int32_t flag = bad ? CSP_RANK_BAD_LABEL : st != st ? CSP_RANK_NAN : 0;
-            a.greater[b] = flag ? flag : ngt;
-            a.tied[b] = flag ? flag : ntie;
-            a.argmax[b] = flag ? flag : bi;
-        }
+        neighbor_rank_row(a.img, a.img_kind, a.labels, a.greater, a.tied, a.argmax, b, C, lane, [&](int c) { return prior_of(row[c]); });
     }
 }
 

@@ -35,6 +35,7 @@
 #include "csp_rank_kernel.h"
 #include "checker_kernel.h"
 #include "neighbor_kernel.h"
+#include "kde_kernel.h"
 
 using namespace range_hip;
 using namespace range_host;
@@ -51,6 +52,7 @@ using namespace range_host;
 #include "csp_host.h"
 #include "checker_host.h"
 #include "neighbor_host.h"
+#include "kde_host.h"
 
 extern "C" {
 

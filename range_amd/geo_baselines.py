@@ -1,6 +1,8 @@
 """The location-only baselines of the CSP evaluation (reference: location_models/csp/main/baselines.py
 ``compute_neighbor_prior`` / ``GridPrior``, trainer.py's train-frequency prior, eval_helper.py
-``get_cross_val_hyper_params``): ``train_freq``, ``nn_dist``, ``nn_knn`` and ``grid``.
+``get_cross_val_hyper_params``): ``train_freq``, ``nn_dist``, ``nn_knn``, ``grid`` and ``kde``
+(``create_kde_grid`` / ``kde_prior``: ``KdePrior``, csrc/kde_kernel.h - per-class sums of Gaussian weights as 64-bit
+fixed-point integers, so that the result depends on no order).
 
 Locations are (lon, lat) DEGREES, as everywhere in this project.  ``NeighborPrior`` plays the part of the
 reference's ``BallTree``: it installs the training set on the GPU once and answers queries with one scan
@@ -221,3 +223,96 @@ class GridPrior(_PriorBase):
         qc = self._qcell(locs)
         lab, img = self._inputs(labels, preds, qc.shape[0])
         return _ranks(self.engine.neighbor_rank(None, qc, _nn.CELL, labels=lab, img=img, pc=self._pc, cpc=self._cpc))
+
+
+#: kde_prior's message for a zero bandwidth
+KDE_ZERO_BANDWIDTH = "All data points are at the same location - try reducing quantization."
+
+
+def create_kde_grid(train_classes, train_locs, hyper_params) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """baselines.py ``create_kde_grid``, vectorised: the training set quantised with ``np.floor(locs / q) * q`` and
+    reduced to the unique (class, ``hashable_loc``) pairs in first-occurrence order -> (``binned_classes`` (M,),
+    ``binned_locs`` (M, 2) - the quantised location of a pair's first occurrence -, ``counts`` (M,) int64), the
+    reference's three arrays bit for bit.  ``hashable_loc`` is ``floor(quantised / q)`` per axis, evaluated on the
+    ALREADY quantised value as there (it can differ from ``floor(x / q)`` by one).  AssertionError: ``kde_quant <=
+    0``; ValueError: a training location that is not finite."""
+    q = hyper_params["kde_quant"]
+    assert q > 0
+    locs = np.asarray(train_locs)
+    classes = np.asarray(train_classes)
+    if locs.ndim != 2 or locs.shape[1] != 2 or classes.shape != (locs.shape[0],):
+        raise ValueError(f"train_locs (N, 2) and train_classes (N,), got {locs.shape} and {classes.shape}")
+    if not np.isfinite(locs).all():
+        row = int(np.flatnonzero(~np.isfinite(locs).all(axis=1))[0])
+        raise ValueError(f"kde prior: training location {row} {tuple(locs[row])} is not finite")
+    quantized = np.floor(locs / q) * q
+    key = np.floor(quantized / q).astype(np.int64)
+    _, cls_id = np.unique(classes, return_inverse=True)
+    rows = np.stack([cls_id.reshape(-1).astype(np.int64), key[:, 0], key[:, 1]], axis=1)
+    _, first, counts = np.unique(rows, axis=0, return_index=True, return_counts=True)
+    order = np.argsort(first, kind="stable")
+    first = first[order]
+    return classes[first], quantized[first], counts[order].astype(np.int64)
+
+
+class KdePrior(_PriorBase):
+    """``kde``: ``train_locs`` (N, 2) (lon, lat) degrees, ``train_classes`` (N,); ``hyper_params`` gives ``kde_quant``,
+    ``kde_nb`` and ``kde_dist_type`` ('haversine' or anything else for euclidean degrees).  Bins the training set on
+    the host once (``create_kde_grid``), installs the bins with their counts, and answers a batch with one selection
+    (the ``kde_nb``-th bin's distance), the reference's bandwidth arithmetic on the host in numpy scalars, and one
+    scan.  A NaN coordinate - longitude or latitude - gives the uniform prior; an infinite one, ``kde_nb`` outside
+    1 .. M and a zero bandwidth raise ValueError."""
+
+    def __init__(self, train_locs, train_classes, num_classes: int, hyper_params: Dict, device=None):
+        self.num_classes = int(num_classes)
+        self.haversine = hyper_params.get("kde_dist_type", "euclidean") == "haversine"
+        self.kde_nb = hyper_params.get("kde_nb")
+        locs = np.asarray(train_locs, dtype=np.float64)
+        if locs.ndim != 2 or locs.shape[1] != 2 or locs.shape[0] < 1:
+            raise ValueError(f"train_locs (N, 2) with N > 0, got {locs.shape}")
+        dev = _device(device)
+        self.binned_classes, self.binned_locs, self.counts = create_kde_grid(np.asarray(train_classes).reshape(-1), locs, hyper_params)
+        self.num_bins = len(self.counts)
+        self.engine = _nn.NeighborEngine(dev)
+        self.engine.set_kde_points(np.deg2rad(self.binned_locs) if self.haversine else self.binned_locs, self.binned_classes,
+                                   self.counts, self.num_classes, self.haversine)
+
+    def _scan_inputs(self, locs):
+        """The batch on the device and its per-row (thr, two_h2) there; h (B,) on the host (NaN for a NaN row)."""
+        if self.kde_nb is None:
+            raise ValueError("hyper_params['kde_nb'] is missing")
+        k = int(self.kde_nb)
+        if k < 1 or k > self.num_bins:
+            raise ValueError(f"kde_nb = {k} of {self.num_bins} bins (1 .. M, as BallTree.query)")
+        q = np.asarray(locs.detach().cpu() if hasattr(locs, "detach") else locs, dtype=np.float64).reshape(-1, 2)
+        if np.isinf(q).any():
+            row = int(np.flatnonzero(np.isinf(q).any(axis=1))[0])
+            raise ValueError(f"kde prior: query row {row} {tuple(q[row])} has an infinite coordinate")
+        dev = self.engine.device
+        qd = torch.from_numpy(np.ascontiguousarray(np.deg2rad(q) if self.haversine else q)).to(dev)
+        red_k = self.engine.neighbor_select(qd, k)[0].cpu().numpy()
+        with np.errstate(invalid="ignore"):
+            d_k = 2 * np.arcsin(np.sqrt(red_k)) if self.haversine else np.sqrt(red_k)       # as kth_distance
+        h = 0.5 * d_k
+        if (h == 0).any():
+            row = int(np.flatnonzero(h == 0)[0])
+            raise ValueError(f"kde prior: query row {row}: {KDE_ZERO_BANDWIDTH}")
+        # numpy scalars, the reference's expressions: r = 2 h + 1e-9, 2 h ** 2 (a scalar ** is pow, not a product)
+        thr = np.array([radius_threshold(2 * x + 1e-9, self.haversine) for x in h], dtype=np.float64)
+        two_h2 = np.array([2 * x ** 2 for x in h], dtype=np.float64)
+        return qd, torch.from_numpy(thr).to(dev), torch.from_numpy(two_h2).to(dev), h
+
+    def prior(self, locs) -> np.ndarray:
+        """(B, num_classes) float64: ``kde_prior`` of every row."""
+        qd, thr, two_h2, _ = self._scan_inputs(locs)
+        return self.engine.kde_prior(qd, thr, two_h2).cpu().numpy()
+
+    def label_ranks(self, locs, labels, preds=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(ranks, predicted classes) of ``preds * prior(locs)``; no row is dropped."""
+        qd, thr, two_h2, _ = self._scan_inputs(locs)
+        lab, img = self._inputs(labels, preds, qd.shape[0])
+        return _ranks(self.engine.kde_rank(qd, thr, two_h2, labels=lab, img=img))
+
+    def bandwidth(self, locs) -> np.ndarray:
+        """The kernel bandwidth ``h = 0.5 d_k`` of every row (radians / degrees); NaN for a NaN location."""
+        return self._scan_inputs(locs)[3]
