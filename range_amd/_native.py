@@ -495,10 +495,9 @@ class HipEngine:
                                                         out.data_ptr(), self._stream()))
         return out
 
-    def _csp_rank_args(self, B: int, img: Optional[torch.Tensor], labels: torch.Tensor):
-        C_ = self.csp_classes
-        if C_ <= 0:
-            raise RangeNativeError("no CSP class head set on this engine (set_csp_head)")
+    def _rank_args(self, B: int, C_: int, img: Optional[torch.Tensor], labels: torch.Tensor):
+        """What every rank call takes beside its rows: ``labels`` (B,) int32, ``img`` (B, C_) float32 / float64 or
+        None -> (the image kind, the three (B,) int32 outputs)."""
         self._t(labels, torch.int32, ())
         if labels.shape[0] != B:
             raise ValueError(f"{labels.shape[0]} labels for {B} rows")
@@ -511,6 +510,12 @@ class HipEngine:
                 raise ValueError(f"{img.shape[0]} rows of image predictions for {B} rows")
             kind = CSP_IMG_F32 if img.dtype == torch.float32 else CSP_IMG_F64
         return kind, tuple(self._empty((B,), torch.int32) for _ in range(3))
+
+    def _csp_rank_args(self, B: int, img: Optional[torch.Tensor], labels: torch.Tensor):
+        C_ = self.csp_classes
+        if C_ <= 0:
+            raise RangeNativeError("no CSP class head set on this engine (set_csp_head)")
+        return self._rank_args(B, C_, img, labels)
 
     def csp_rank(self, feats: Optional[torch.Tensor], labels: torch.Tensor, img: Optional[torch.Tensor] = None,
                  max_grid: int = 0, col_parts: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -66,22 +66,22 @@ def load_library() -> C.CDLL:
     return lib
 
 
-def plan(B: int, N: int, num_classes: int, k: int = 0, max_grid: int = 0, chunks: int = 0) -> Dict[str, int]:
-    """The launch plan (host_plan.h: neighbor_plan); needs no GPU."""
+def _plan(entry: str, args: Tuple[int, ...], own_keys: Tuple[str, str]) -> Dict[str, int]:
     lib = load_library()
     out = np.zeros(8, dtype=np.int64)
-    _check(lib, lib.range_neighbor_plan(B, N, num_classes, k, max_grid, chunks, out.ctypes.data))
-    keys = ("group", "groups", "grid", "chunks", "lds_bytes", "ws_bytes", "digit_bits", "passes")
+    _check(lib, getattr(lib, entry)(*args, out.ctypes.data))
+    keys = ("group", "groups", "grid", "chunks", "lds_bytes", "ws_bytes") + own_keys
     return dict(zip(keys, (int(v) for v in out)))
+
+
+def plan(B: int, N: int, num_classes: int, k: int = 0, max_grid: int = 0, chunks: int = 0) -> Dict[str, int]:
+    """The launch plan (host_plan.h: neighbor_plan); needs no GPU."""
+    return _plan("range_neighbor_plan", (B, N, num_classes, k, max_grid, chunks), ("digit_bits", "passes"))
 
 
 def kde_plan(B: int, M: int, num_classes: int, total_count: int, max_grid: int = 0, chunks: int = 0) -> Dict[str, int]:
     """The KDE prior's launch plan (host_plan.h: kde_plan); needs no GPU."""
-    lib = load_library()
-    out = np.zeros(8, dtype=np.int64)
-    _check(lib, lib.range_kde_plan(B, M, num_classes, total_count, max_grid, chunks, out.ctypes.data))
-    keys = ("group", "groups", "grid", "chunks", "lds_bytes", "ws_bytes", "scale_bits", "tiles")
-    return dict(zip(keys, (int(v) for v in out)))
+    return _plan("range_kde_plan", (B, M, num_classes, total_count, max_grid, chunks), ("scale_bits", "tiles"))
 
 
 class NeighborEngine(HipEngine):
@@ -143,19 +143,7 @@ class NeighborEngine(HipEngine):
         """(``greater``, ``tied_after``, ``argmax``), (B,) int32 each, as ``HipEngine.csp_rank`` gives them, over
         the scores ``img.double() * prior`` (range_neighbor_rank_grid)."""
         B = self._queries(q, qcell, mode)
-        C_ = self.neighbor_classes
-        self._t(labels, torch.int32, ())
-        if labels.shape[0] != B:
-            raise ValueError(f"{labels.shape[0]} labels for {B} rows")
-        kind = CSP_IMG_NONE
-        if img is not None:
-            if img.dtype not in (torch.float32, torch.float64):
-                raise ValueError(f"image predictions must be float32 or float64, got {img.dtype}")
-            self._t(img, img.dtype, (C_,))
-            if img.shape[0] != B:
-                raise ValueError(f"{img.shape[0]} rows of image predictions for {B} rows")
-            kind = CSP_IMG_F32 if img.dtype == torch.float32 else CSP_IMG_F64
-        out = tuple(self._empty((B,), torch.int32) for _ in range(3))
+        kind, out = self._rank_args(B, self.neighbor_classes, img, labels)
         if B:
             _check(self.lib, self.lib.range_neighbor_rank_grid(
                 self._h, _ptr(q), _ptr(qcell), B, mode, int(k), float(thr), float(pc), float(cpc), _ptr(img), kind,
@@ -213,19 +201,7 @@ class NeighborEngine(HipEngine):
         """(``greater``, ``tied_after``, ``argmax``), (B,) int32 each, over ``img.double() * prior``
         (range_kde_rank_grid)."""
         B = self._kde_inputs(q, thr, two_h2)
-        C_ = self.neighbor_classes
-        self._t(labels, torch.int32, ())
-        if labels.shape[0] != B:
-            raise ValueError(f"{labels.shape[0]} labels for {B} rows")
-        kind = CSP_IMG_NONE
-        if img is not None:
-            if img.dtype not in (torch.float32, torch.float64):
-                raise ValueError(f"image predictions must be float32 or float64, got {img.dtype}")
-            self._t(img, img.dtype, (C_,))
-            if img.shape[0] != B:
-                raise ValueError(f"{img.shape[0]} rows of image predictions for {B} rows")
-            kind = CSP_IMG_F32 if img.dtype == torch.float32 else CSP_IMG_F64
-        out = tuple(self._empty((B,), torch.int32) for _ in range(3))
+        kind, out = self._rank_args(B, self.neighbor_classes, img, labels)
         if B:
             _check(self.lib, self.lib.range_kde_rank_grid(
                 self._h, q.data_ptr(), thr.data_ptr(), two_h2.data_ptr(), B, _ptr(img), kind, labels.data_ptr(),

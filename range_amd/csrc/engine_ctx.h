@@ -145,8 +145,7 @@ struct range_ctx {
         bool hav = false, has_cells = false;
         int kde_bits = 0;                // > 0: a weighted set, the scale bits of its fixed-point sums
         DevBuf<NeighborPoint> d_pts;
-        DevBuf<int32_t> ws_counts;
-        DevBuf<uint64_t> ws_sums;        // a split KDE scan's partial rows
+        DevBuf<uint64_t> ws_rows;        // a split scan's partial rows of either kind, sized in bytes (plan: ws_bytes)
         DevBuf<double> ws_redk;
         DevBuf<int64_t> ws_jlast;
     } nb;

@@ -1147,10 +1147,21 @@ struct NeighborPlan {
     static constexpr int shift_of(int pass) { return (NEIGHBOR_PASSES - 1 - pass) * NEIGHBOR_DIGIT_BITS; }
 };
 
-// queries a workgroup for C classes (0: C outside 1 .. NEIGHBOR_MAX_CLASSES)
-inline int neighbor_group(int C) {
-    if (C < 1 || C > NEIGHBOR_MAX_CLASSES) return 0;
-    return (int)std::min<size_t>(NEIGHBOR_MAX_GROUP, NEIGHBOR_COUNT_LDS / ((size_t)C * 4));
+// queries a workgroup for C classes whose rows have `entry`-byte entries (0: C outside 1 .. max_classes)
+inline int neighbor_group_of(int C, size_t entry, int max_classes) {
+    if (C < 1 || C > max_classes) return 0;
+    return (int)std::min<size_t>(NEIGHBOR_MAX_GROUP, NEIGHBOR_COUNT_LDS / ((size_t)C * entry));
+}
+inline int neighbor_group(int C) { return neighbor_group_of(C, 4, NEIGHBOR_MAX_CLASSES); }
+
+// what every scan's plan refuses of B queries, `points` training points or bins (N or M in the text), max_grid and
+// chunks, with the plan's `own` refusal (or null) at its place in the order: the reason, or null
+inline const char* neighbor_plan_refusal(int64_t B, int64_t points, bool bins, const char* own, int64_t max_grid, int chunks) {
+    if (B < 1 || B > NEIGHBOR_MAX_QUERIES) return "B outside 1 .. 2^31 - 1";
+    if (points < 1 || points > NEIGHBOR_MAX_POINTS) return bins ? "M outside 1 .. 2^31 - 1" : "N outside 1 .. 2^31 - 1";
+    if (own) return own;
+    if (max_grid < 0 || chunks < 0) return "max_grid or chunks below 0";
+    return nullptr;
 }
 
 // the geometry of a vote scan whose LDS rows have `entry`-byte entries and G = `group` rows a workgroup: groups,
@@ -1180,11 +1191,10 @@ inline void neighbor_plan_rows(NeighborPlan& p, int64_t B, int64_t N, int C, int
 // most n chunks (never more than the tiles, NEIGHBOR_MAX_CHUNKS or what the workspace cap allows).
 inline NeighborPlan neighbor_plan(int64_t B, int64_t N, int C, int64_t k, int64_t max_grid = 0, int chunks = 0) {
     NeighborPlan p;
-    if (B < 1 || B > NEIGHBOR_MAX_QUERIES) { p.why = "B outside 1 .. 2^31 - 1"; return p; }
-    if (N < 1 || N > NEIGHBOR_MAX_POINTS) { p.why = "N outside 1 .. 2^31 - 1"; return p; }
-    if (C < 1 || C > NEIGHBOR_MAX_CLASSES) { p.why = "num_classes outside 1 .. 32768 (one count row of LDS)"; return p; }
-    if (k < 0 || k > N) { p.why = "k outside 1 .. N"; return p; }
-    if (max_grid < 0 || chunks < 0) { p.why = "max_grid or chunks below 0"; return p; }
+    const char* const own = C < 1 || C > NEIGHBOR_MAX_CLASSES ? "num_classes outside 1 .. 32768 (one count row of LDS)"
+                            : k < 0 || k > N                  ? "k outside 1 .. N"
+                                                              : nullptr;
+    if (const char* why = neighbor_plan_refusal(B, N, false, own, max_grid, chunks)) { p.why = why; return p; }
     neighbor_plan_rows(p, B, N, C, max_grid, chunks, 4, neighbor_group(C));
     p.valid = true;
     return p;
@@ -1203,10 +1213,7 @@ struct KdePlan : NeighborPlan {
     int scale_bits = 0;
 };
 
-inline int kde_group(int C) {
-    if (C < 1 || C > KDE_MAX_CLASSES) return 0;
-    return (int)std::min<size_t>(NEIGHBOR_MAX_GROUP, NEIGHBOR_COUNT_LDS / ((size_t)C * 8));
-}
+inline int kde_group(int C) { return neighbor_group_of(C, 8, KDE_MAX_CLASSES); }
 
 // (0: total_count outside 1 .. KDE_MAX_TOTAL)
 inline int kde_scale_bits(int64_t total_count) {
@@ -1219,11 +1226,10 @@ inline int kde_scale_bits(int64_t total_count) {
 // B queries, M bins, C classes, total_count the sum of the bins' counts; max_grid and chunks as neighbor_plan's
 inline KdePlan kde_plan(int64_t B, int64_t M, int C, int64_t total_count, int64_t max_grid = 0, int chunks = 0) {
     KdePlan p;
-    if (B < 1 || B > NEIGHBOR_MAX_QUERIES) { p.why = "B outside 1 .. 2^31 - 1"; return p; }
-    if (M < 1 || M > NEIGHBOR_MAX_POINTS) { p.why = "M outside 1 .. 2^31 - 1"; return p; }
-    if (C < 1 || C > KDE_MAX_CLASSES) { p.why = "num_classes outside 1 .. 16384 (one row of 64-bit sums in LDS)"; return p; }
-    if (total_count < M || total_count > KDE_MAX_TOTAL) { p.why = "total count outside M .. 2^31 - 1"; return p; }
-    if (max_grid < 0 || chunks < 0) { p.why = "max_grid or chunks below 0"; return p; }
+    const char* const own = C < 1 || C > KDE_MAX_CLASSES                    ? "num_classes outside 1 .. 16384 (one row of 64-bit sums in LDS)"
+                            : total_count < M || total_count > KDE_MAX_TOTAL ? "total count outside M .. 2^31 - 1"
+                                                                             : nullptr;
+    if (const char* why = neighbor_plan_refusal(B, M, true, own, max_grid, chunks)) { p.why = why; return p; }
     neighbor_plan_rows(p, B, M, C, max_grid, chunks, 8, kde_group(C));
     p.scale_bits = kde_scale_bits(total_count);
     p.valid = true;

@@ -18,52 +18,21 @@ static int kde_run(range_ctx* c, const double* q, const double* thr, const doubl
                    int64_t max_grid, int32_t chunks, range_stream_t stream) {
     if (!c || !q || !thr || !two_h2) return fail(RANGE_ERR_INVALID, "null argument");
     if (int rc = need_kde_points(c)) return rc;
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (max_grid < 0 || chunks < 0) return fail(RANGE_ERR_INVALID, "max_grid and chunks must be >= 0");
-    if (greater) {
-        if (!labels || !tied || !argmax) return fail(RANGE_ERR_INVALID, "null argument");
-        if (int rc = check_img_kind(img, img_kind)) return rc;
-    }
-    if (!aligned(q, 8) || !aligned(thr, 8) || !aligned(two_h2, 8) || !aligned(labels, 4) || !aligned(greater, 4) || !aligned(tied, 4) ||
-        !aligned(argmax, 4) || !aligned(prior, 8) || !aligned(sums, 8) || !aligned(img, img_kind == CSP_IMG_F64 ? 8 : 4))
-        return fail(RANGE_ERR_INVALID, "the device pointers must be aligned to their element");
+    if (int rc = neighbor_check_scan(B, max_grid, chunks, nullptr, img, img_kind, labels, greater, tied, argmax, prior,
+                                     aligned(q, 8) && aligned(thr, 8) && aligned(two_h2, 8) && aligned(sums, 8)))
+        return rc;
     range_ctx::Neighbors& m = c->nb;
     // (the total count enters the plan through the scale bits alone, which the installation fixed)
     const KdePlan p = kde_plan(B, m.N, m.C, m.N, max_grid, chunks);
     if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld: %s", (long long)B, p.why);
     ENTER_DEVICE(c);
-    const hipStream_t s = (hipStream_t)stream;
     KdeArgs a{};
-    a.pts = m.d_pts.p;
-    a.M = m.N;
-    a.n_tiles = p.n_tiles;
-    a.q = q;
+    neighbor_fill_scan(a, m, p, q, B, img, img_kind, labels, greater, tied, argmax, prior);
     a.thr = thr;
     a.two_h2 = two_h2;
-    a.B = B;
-    a.groups = p.groups;
-    a.G = p.group;
-    a.C = m.C;
     a.scale = std::ldexp(1.0, m.kde_bits);
-    a.img = greater ? img : nullptr;
-    a.img_kind = greater ? img_kind : CSP_IMG_NONE;
-    a.labels = labels;
-    a.greater = greater;
-    a.tied = tied;
-    a.argmax = argmax;
-    a.prior = prior;
-    a.sums = sums;
-    a.chunks = p.chunks;
-    if (p.chunks > 1) {
-        if (m.ws_sums.ensure(p.ws_ints) != hipSuccess)
-            return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of partial sums)", p.ws_bytes);
-        a.ws = m.ws_sums.p;
-    }
-    if (int rc = launch(m.hav ? kde_vote_kernel<true> : kde_vote_kernel<false>, dim3(p.grid, (unsigned)p.chunks), dim3(p.vote_block),
-                        p.lds_bytes, s, a))
-        return rc;
-    if (p.chunks == 1) return RANGE_OK;
-    return launch(kde_fold_kernel, dim3(p.fold_grid), dim3(p.vote_block), p.lds_bytes, s, a);
+    a.raw = sums;
+    return neighbor_launch_scan(c, p, m.hav ? kde_vote_kernel<true> : kde_vote_kernel<false>, kde_fold_kernel, a, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -73,12 +42,7 @@ int range_kde_plan(int64_t B, int64_t M, int32_t C, int64_t total_count, int64_t
     const KdePlan p = kde_plan(B, M, C, total_count, max_grid, chunks);
     if (!p.valid)
         return fail(RANGE_ERR_INVALID, "B = %lld, M = %lld, C = %d, total count %lld: %s", (long long)B, (long long)M, C, (long long)total_count, p.why);
-    out[0] = p.group;
-    out[1] = p.groups;
-    out[2] = p.grid;
-    out[3] = p.chunks;
-    out[4] = (int64_t)p.lds_bytes;
-    out[5] = (int64_t)p.ws_bytes;
+    neighbor_plan_out(p, out);
     out[6] = p.scale_bits;
     out[7] = p.n_tiles;
     return RANGE_OK;

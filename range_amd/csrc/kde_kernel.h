@@ -25,9 +25,8 @@
 // m = min over I_c > 0:  prior[c] = ((double) I_c + (double) m) / ((double) S + (double) C * (double) m), and 1.0 / C
 // when S == 0 (a NaN query).  Score, greater / tied_after / argmax and their flags: neighbor_rank_row.
 //
-// WORK SPLIT (host_plan.h: kde_plan): neighbor_vote_kernel's - G queries a workgroup (uint64 rows: half as many),
-// 1024 threads, tiles of 256, NEIGHBOR_UNROLL trips of loads in flight, chunks over grid y; with more than one
-// chunk the partial uint64 rows go to the workspace and kde_fold_kernel adds them and ranks.
+// WORK SPLIT (host_plan.h: kde_plan): neighbor_kernel.h's scan and fold over the row policy KdeRows below (uint64
+// rows: half as many queries a workgroup).
 #pragma once
 #include "neighbor_kernel.h"
 
@@ -40,23 +39,11 @@ struct KdeQuery {            // NEIGHBOR_QUERY_LDS bytes
 };
 static_assert(sizeof(KdeQuery) == range_host::NEIGHBOR_QUERY_LDS, "layout");
 
-struct KdeArgs {
-    const NeighborPoint* pts;        // `cell` is the bin's count
-    int64_t M, n_tiles;
-    const double* q;                 // (B, 2) (lon, lat): radians (haversine) or degrees
+struct KdeArgs : NeighborScanArgs {  // (the `cell` of pts is the bin's count, N their number M)
     const double* thr;               // (B)
     const double* two_h2;            // (B)
-    int64_t B, groups;
-    int32_t G, C;
     double scale;                    // 2^s
-    const void* img;                 // (B, C) float32 / float64 or null
-    int32_t img_kind;
-    const int32_t* labels;           // (B), with greater / tied / argmax
-    int32_t *greater, *tied, *argmax;
-    double* prior;                   // (B, C) or null
-    uint64_t* sums;                  // (B, C) or null
-    uint64_t* ws;                    // chunks > 1: (chunks, groups, G * C) partial rows
-    int32_t chunks;                  // fold: how many
+    uint64_t *raw, *ws;              // the sums
 };
 
 // the squared distance the reference weighs a member by
@@ -83,15 +70,40 @@ __device__ __forceinline__ uint64_t kde_fixed(double dist, double two_h2, double
     return (uint64_t)rint(w * scale);
 }
 
-// the rows of a group, a wave each: sums / priors on request, the three integers
-__device__ __forceinline__ void kde_rank_group(const KdeArgs& a, const uint64_t* rows, int64_t b0, int live) {
+// the KDE rows: uint64 fixed-point sums of the members' weights under metric HAV (the fold and the ranks read no record)
+template <bool HAV>
+struct KdeRows {
+    using Entry = uint64_t;
+    using Query = KdeQuery;
+    using Args = KdeArgs;
+
+    static __device__ __forceinline__ void stage(const Args& a, Query& out, int64_t b, bool live) {
+        Query q;
+        q.lat = q.lon = q.thr = q.two_h2 = __builtin_nan("");
+        q.cs = q.pad = 0.0;
+        if (live) {
+            q.lon = a.q[2 * b];
+            q.lat = a.q[2 * b + 1];
+            q.cs = HAV ? cos(q.lat) : 0.0;
+            q.thr = a.thr[b];
+            q.two_h2 = a.two_h2[b];
+        }
+        out = q;
+    }
+
+    static __device__ __forceinline__ void stage_fold(const Args&, Query&, int64_t, bool) {}
+
+    static __device__ __forceinline__ void member(const Args& a, const Query& q, const NeighborPoint& p, int64_t, Entry* row) {
+        const double red = neighbor_red<HAV>(q.lon, q.lat, q.cs, p.lon, p.lat, p.cs);
+        if (red <= q.thr) {
+            const uint64_t v = kde_fixed(kde_dist<HAV>(q, p, red), q.two_h2, a.scale);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&row[p.cls]), (unsigned long long)((uint64_t)(uint32_t)p.cell * v));
+        }
+    }
+
+    static __device__ __forceinline__ auto prior_of(const Args& a, const Query&, const Entry* row, int lane) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int C = a.C;
-    for (int g = wave; g < live; g += NEIGHBOR_VOTE_BLOCK / 64) {
-        const uint64_t* const row = rows + (size_t)g * C;
-        const int64_t b = b0 + g;
+        const int C = a.C;
         uint64_t sum = 0, mn = ~UINT64_C(0);
         for (int c = lane; c < C; c += 64) {
             const uint64_t v = row[c];
@@ -107,98 +119,17 @@ __device__ __forceinline__ void kde_rank_group(const KdeArgs& a, const uint64_t*
         const bool uniform = sum == 0;
         const double m = (double)mn, one_c = 1.0 / (double)C;
         const double den = (double)sum + (double)C * m;
-        const auto prior_of = [&](uint64_t v) { return uniform ? one_c : ((double)v + m) / den; };
-        if (a.sums)
-            for (int c = lane; c < C; c += 64) a.sums[b * C + c] = row[c];
-        if (a.prior)
-            for (int c = lane; c < C; c += 64) a.prior[b * C + c] = prior_of(row[c]);
-        if (!a.greater) continue;
-        neighbor_rank_row(a.img, a.img_kind, a.labels, a.greater, a.tied, a.argmax, b, C, lane, [&](int c) { return prior_of(row[c]); });
+        return [=](uint64_t v) { return uniform ? one_c : ((double)v + m) / den; };
     }
-}
+};
 
 template <bool HAV>
 __global__ __launch_bounds__(NEIGHBOR_VOTE_BLOCK) void kde_vote_kernel(KdeArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t kde_lds[];
-    const int t = threadIdx.x;
-    const int G = a.G, C = a.C;
-    const int row_words = G * C;                                  // at most NEIGHBOR_COUNT_LDS / 8
-    uint64_t* const rows = kde_lds;
-    KdeQuery* const qs = reinterpret_cast<KdeQuery*>(kde_lds + ((row_words + 1) & ~1));
-    for (int64_t grp = blockIdx.x; grp < a.groups; grp += gridDim.x) {
-        const int64_t b0 = grp * G;
-        const int live = a.B - b0 < G ? (int)(a.B - b0) : G;
-        __syncthreads();                                          // the last group's rows have been read
-        for (int i = t; i < row_words; i += NEIGHBOR_VOTE_BLOCK) rows[i] = 0;
-        if (t < G) {                                              // the rows beyond B never have a member
-            KdeQuery q;
-            q.lat = q.lon = q.thr = q.two_h2 = __builtin_nan("");
-            q.cs = q.pad = 0.0;
-            if (t < live) {
-                q.lon = a.q[2 * (b0 + t)];
-                q.lat = a.q[2 * (b0 + t) + 1];
-                q.cs = HAV ? cos(q.lat) : 0.0;
-                q.thr = a.thr[b0 + t];
-                q.two_h2 = a.two_h2[b0 + t];
-            }
-            qs[t] = q;
-        }
-        __syncthreads();
-        // neighbor_vote_kernel's walk: NEIGHBOR_VOTE_SUBS tiles side by side, NEIGHBOR_UNROLL trips' loads together
-        const int sub = t / NEIGHBOR_BLOCK, tt = t % NEIGHBOR_BLOCK;
-        for (int64_t tile0 = blockIdx.y; tile0 < a.n_tiles; tile0 += (int64_t)NEIGHBOR_UNROLL * NEIGHBOR_VOTE_SUBS * gridDim.y) {
-            NeighborPoint p[NEIGHBOR_UNROLL];
-            int64_t j[NEIGHBOR_UNROLL];
-#pragma unroll
-            for (int u = 0; u < NEIGHBOR_UNROLL; ++u) {
-                const int64_t tile = tile0 + (int64_t)(u * NEIGHBOR_VOTE_SUBS + sub) * gridDim.y;
-                j[u] = tile < a.n_tiles ? tile * NEIGHBOR_BLOCK + tt : a.M;
-                if (j[u] < a.M) p[u] = a.pts[j[u]];
-            }
-#pragma unroll
-            for (int u = 0; u < NEIGHBOR_UNROLL; ++u) {
-                if (j[u] < a.M) {
-                    for (int g = 0; g < live; ++g) {
-                        const KdeQuery& q = qs[g];
-                        const double red = neighbor_red<HAV>(q.lon, q.lat, q.cs, p[u].lon, p[u].lat, p[u].cs);
-                        if (red <= q.thr) {
-                            const uint64_t v = kde_fixed(kde_dist<HAV>(q, p[u], red), q.two_h2, a.scale);
-                            atomicAdd(reinterpret_cast<unsigned long long*>(&rows[g * C + p[u].cls]),
-                                      (unsigned long long)((uint64_t)(uint32_t)p[u].cell * v));
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (gridDim.y > 1) {
-            uint64_t* const out = a.ws + ((int64_t)blockIdx.y * a.groups + grp) * row_words;
-            for (int i = t; i < row_words; i += NEIGHBOR_VOTE_BLOCK) out[i] = rows[i];
-        } else {
-            kde_rank_group(a, rows, b0, live);
-        }
-    }
+    neighbor_vote_body<KdeRows<HAV>>(a);
 }
 
-// the chunks' partial rows of a group, added in LDS, then ranked as the unsplit scan ranks them
 __global__ __launch_bounds__(NEIGHBOR_VOTE_BLOCK) void kde_fold_kernel(KdeArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t kde_lds[];
-    const int t = threadIdx.x;
-    const int G = a.G, C = a.C;
-    const int row_words = G * C;
-    uint64_t* const rows = kde_lds;
-    for (int64_t grp = blockIdx.x; grp < a.groups; grp += gridDim.x) {
-        const int64_t b0 = grp * G;
-        const int live = a.B - b0 < G ? (int)(a.B - b0) : G;
-        __syncthreads();
-        for (int i = t; i < row_words; i += NEIGHBOR_VOTE_BLOCK) {
-            uint64_t n = 0;
-            for (int y = 0; y < a.chunks; ++y) n += a.ws[((int64_t)y * a.groups + grp) * row_words + i];
-            rows[i] = n;
-        }
-        __syncthreads();
-        kde_rank_group(a, rows, b0, live);
-    }
+    neighbor_fold_body<KdeRows<false>>(a);
 }
 
 }  // namespace range_hip

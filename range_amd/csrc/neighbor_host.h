@@ -79,6 +79,61 @@ static int neighbor_select_impl(range_ctx* c, const double* q, int64_t B, int64_
     return launch(c->nb.hav ? neighbor_select_kernel<true> : neighbor_select_kernel<false>, dim3(p.select_grid), dim3(p.block), 0, s, a);
 }
 
+// ---- what the scans of both row kinds share (neighbor_run here, kde_run in kde_host.h)
+
+// the checks of the common arguments; own: the caller's refusal of an argument of its own (or null), at its place
+// in the order; own_aligned: the caller's own device pointers are aligned to their element
+static int neighbor_check_scan(int64_t B, int64_t max_grid, int32_t chunks, const char* own, const void* img, int32_t img_kind,
+                               const int32_t* labels, const int32_t* greater, const int32_t* tied, const int32_t* argmax,
+                               const double* prior, bool own_aligned) {
+    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
+    if (max_grid < 0 || chunks < 0) return fail(RANGE_ERR_INVALID, "max_grid and chunks must be >= 0");
+    if (own) return fail(RANGE_ERR_INVALID, "%s", own);
+    if (greater) {
+        if (!labels || !tied || !argmax) return fail(RANGE_ERR_INVALID, "null argument");
+        if (int rc = check_img_kind(img, img_kind)) return rc;
+    }
+    if (!own_aligned || !aligned(labels, 4) || !aligned(greater, 4) || !aligned(tied, 4) || !aligned(argmax, 4) || !aligned(prior, 8) ||
+        !aligned(img, img_kind == CSP_IMG_F64 ? 8 : 4))
+        return fail(RANGE_ERR_INVALID, "the device pointers must be aligned to their element");
+    return RANGE_OK;
+}
+
+// the common part of a scan's arguments from the installed set and the plan
+static void neighbor_fill_scan(NeighborScanArgs& a, const range_ctx::Neighbors& m, const NeighborPlan& p, const double* q, int64_t B,
+                               const void* img, int32_t img_kind, const int32_t* labels, int32_t* greater, int32_t* tied,
+                               int32_t* argmax, double* prior) {
+    a.pts = m.d_pts.p;
+    a.N = m.N;
+    a.n_tiles = p.n_tiles;
+    a.q = q;
+    a.B = B;
+    a.groups = p.groups;
+    a.G = p.group;
+    a.C = m.C;
+    a.img = greater ? img : nullptr;
+    a.img_kind = greater ? img_kind : CSP_IMG_NONE;
+    a.labels = labels;
+    a.greater = greater;
+    a.tied = tied;
+    a.argmax = argmax;
+    a.prior = prior;
+    a.chunks = p.chunks;
+}
+
+// the vote launch over (groups, chunks) and, with more than one chunk, the workspace before it and the fold behind it
+template <class Args>
+static int neighbor_launch_scan(range_ctx* c, const NeighborPlan& p, void (*vote)(Args), void (*fold)(Args), Args& a, hipStream_t s) {
+    if (p.chunks > 1) {
+        if (c->nb.ws_rows.ensure((p.ws_bytes + 7) / 8) != hipSuccess)
+            return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of partial rows)", p.ws_bytes);
+        a.ws = reinterpret_cast<decltype(a.ws)>(c->nb.ws_rows.p);
+    }
+    if (int rc = launch(vote, dim3(p.grid, (unsigned)p.chunks), dim3(p.vote_block), p.lds_bytes, s, a)) return rc;
+    if (p.chunks == 1) return RANGE_OK;
+    return launch(fold, dim3(p.fold_grid), dim3(p.vote_block), p.lds_bytes, s, a);
+}
+
 // the vote scan (and the fold) of B queries into whichever outputs are given
 static int neighbor_run(range_ctx* c, const double* q, const int32_t* qcell, int64_t B, int32_t mode, int64_t k, double thr,
                         double pc, double cpc, const void* img, int32_t img_kind, const int32_t* labels, int32_t* greater,
@@ -90,43 +145,22 @@ static int neighbor_run(range_ctx* c, const double* q, const int32_t* qcell, int
     if (mode == NEIGHBOR_CELL ? (!qcell || !c->nb.has_cells) : !q)
         return fail(RANGE_ERR_INVALID, mode == NEIGHBOR_CELL ? "the cell predicate needs qcell and a training set installed with cells"
                                                              : "null queries");
-    if (B <= 0) return fail(RANGE_ERR_INVALID, "B must be > 0");
-    if (max_grid < 0 || chunks < 0) return fail(RANGE_ERR_INVALID, "max_grid and chunks must be >= 0");
-    if (mode == NEIGHBOR_RADIUS && thr != thr) return fail(RANGE_ERR_INVALID, "the threshold is NaN");
-    if (greater) {
-        if (!labels || !tied || !argmax) return fail(RANGE_ERR_INVALID, "null argument");
-        if (int rc = check_img_kind(img, img_kind)) return rc;
-    }
-    if (!aligned(q, 8) || !aligned(qcell, 4) || !aligned(labels, 4) || !aligned(greater, 4) || !aligned(tied, 4) || !aligned(argmax, 4) ||
-        !aligned(prior, 8) || !aligned(counts, 4) || !aligned(img, img_kind == CSP_IMG_F64 ? 8 : 4))
-        return fail(RANGE_ERR_INVALID, "the device pointers must be aligned to their element");
+    if (int rc = neighbor_check_scan(B, max_grid, chunks, mode == NEIGHBOR_RADIUS && thr != thr ? "the threshold is NaN" : nullptr, img,
+                                     img_kind, labels, greater, tied, argmax, prior,
+                                     aligned(q, 8) && aligned(qcell, 4) && aligned(counts, 4)))
+        return rc;
     range_ctx::Neighbors& m = c->nb;
     const NeighborPlan p = neighbor_plan(B, m.N, m.C, mode == NEIGHBOR_KNN ? k : 0, max_grid, chunks);
     if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld, k = %lld: %s", (long long)B, (long long)k, p.why);
     ENTER_DEVICE(c);
     const hipStream_t s = (hipStream_t)stream;
     NeighborArgs a{};
-    a.pts = m.d_pts.p;
-    a.N = m.N;
-    a.n_tiles = p.n_tiles;
-    a.q = q;
+    neighbor_fill_scan(a, m, p, q, B, img, img_kind, labels, greater, tied, argmax, prior);
     a.qcell = qcell;
-    a.B = B;
-    a.groups = p.groups;
-    a.G = p.group;
-    a.C = m.C;
     a.thr = thr;
     a.pc = pc;
     a.cpc = cpc;
-    a.img = greater ? img : nullptr;
-    a.img_kind = greater ? img_kind : CSP_IMG_NONE;
-    a.labels = labels;
-    a.greater = greater;
-    a.tied = tied;
-    a.argmax = argmax;
-    a.prior = prior;
-    a.counts = counts;
-    a.chunks = p.chunks;
+    a.raw = counts;
     if (mode == NEIGHBOR_KNN) {
         if (m.ws_redk.ensure((size_t)B) != hipSuccess || m.ws_jlast.ensure((size_t)B) != hipSuccess)
             return fail(RANGE_ERR_NOMEM, "out of device memory (%lld selections)", (long long)B);
@@ -134,15 +168,17 @@ static int neighbor_run(range_ctx* c, const double* q, const int32_t* qcell, int
         a.red_k = m.ws_redk.p;
         a.j_last = m.ws_jlast.p;
     }
-    if (p.chunks > 1) {
-        if (m.ws_counts.ensure(p.ws_ints) != hipSuccess)
-            return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of partial counts)", p.ws_bytes);
-        a.ws = m.ws_counts.p;
-    }
-    if (int rc = launch(neighbor_vote_kernel_for(mode, m.hav), dim3(p.grid, (unsigned)p.chunks), dim3(p.vote_block), p.lds_bytes, s, a))
-        return rc;
-    if (p.chunks == 1) return RANGE_OK;
-    return launch(neighbor_fold_kernel_for(mode), dim3(p.fold_grid), dim3(p.vote_block), p.lds_bytes, s, a);
+    return neighbor_launch_scan(c, p, neighbor_vote_kernel_for(mode, m.hav), neighbor_fold_kernel_for(mode), a, s);
+}
+
+// the six leading slots of range_neighbor_plan's and range_kde_plan's out[]
+static void neighbor_plan_out(const NeighborPlan& p, int64_t* out) {
+    out[0] = p.group;
+    out[1] = p.groups;
+    out[2] = p.grid;
+    out[3] = p.chunks;
+    out[4] = (int64_t)p.lds_bytes;
+    out[5] = (int64_t)p.ws_bytes;
 }
 
 extern "C" {
@@ -151,12 +187,7 @@ int range_neighbor_plan(int64_t B, int64_t N, int32_t C, int64_t k, int64_t max_
     if (!out) return fail(RANGE_ERR_INVALID, "null argument");
     const NeighborPlan p = neighbor_plan(B, N, C, k, max_grid, chunks);
     if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld, N = %lld, C = %d, k = %lld: %s", (long long)B, (long long)N, C, (long long)k, p.why);
-    out[0] = p.group;
-    out[1] = p.groups;
-    out[2] = p.grid;
-    out[3] = p.chunks;
-    out[4] = (int64_t)p.lds_bytes;
-    out[5] = (int64_t)p.ws_bytes;
+    neighbor_plan_out(p, out);
     out[6] = NEIGHBOR_DIGIT_BITS;
     out[7] = NEIGHBOR_PASSES;
     return RANGE_OK;

@@ -23,13 +23,15 @@
 // score s[c] = (double) img[c] * prior[c], or prior[c] without image predictions; greater / tied_after / argmax and
 // their -1 / -2 flags are csp_rank_kernel.h's, by its csp_rank_before.
 //
-// WORK SPLIT (host_plan.h: neighbor_plan).  neighbor_vote_kernel: a workgroup owns G queries, their parameters
-// (wave-uniform LDS reads) and zeroed count rows; its 1024 threads walk the packed training points (32 bytes a
+// WORK SPLIT (host_plan.h: neighbor_plan, kde_plan).  One scan (neighbor_vote_body) and one fold (neighbor_fold_body)
+// serve every prior here and the KDE prior of kde_kernel.h; a ROW POLICY says what a row holds: the entry type
+// (int32 votes, uint64 fixed-point sums), the query's record of NEIGHBOR_QUERY_LDS bytes and how it is loaded, what a
+// member adds to its class entry, and the row's statistic behind prior_of.  A workgroup owns G queries, their
+// records (wave-uniform LDS reads) and zeroed rows; its 1024 threads walk the packed training points (32 bytes a
 // point, cos lat formed once by neighbor_prep_kernel) in tiles of 256, four tiles side by side, each thread its
-// point against the G queries; a member costs one LDS integer add.  Integer adds are order-free: the counts depend
-// on no split.  With one chunk each wave then ranks rows of the group from LDS; with more, chunk y stores its rows
-// to the workspace and neighbor_fold_kernel adds the chunks in LDS and ranks - the same integers, hence the same
-// bits.
+// point against the G queries; a member costs one LDS integer add.  Integer adds are order-free: the rows depend on
+// no split.  With one chunk each wave then ranks rows of the group from LDS; with more, chunk y stores its rows to
+// the workspace and the fold adds the chunks in LDS and ranks - the same integers, hence the same bits.
 //
 // SELECTION.  neighbor_select_kernel, a workgroup a query: the k-th smallest (red, j) by a radix select over the
 // key of red - its bit pattern with the sign bit flipped (all bits for a negative value), which orders as red does.
@@ -73,25 +75,29 @@ struct NeighborQuery {       // NEIGHBOR_QUERY_LDS bytes
 };
 static_assert(sizeof(NeighborPoint) == 32 && sizeof(NeighborQuery) == range_host::NEIGHBOR_QUERY_LDS, "layout");
 
-struct NeighborArgs {
+// what every row policy's scan and fold take; `raw` (B, C) or null - the rows themselves - and `ws` - chunks > 1:
+// (chunks, groups, G * C) partial rows - are of the policy's entry type and stand in its own struct
+struct NeighborScanArgs {
     const NeighborPoint* pts;
     int64_t N, n_tiles;
     const double* q;                 // (B, 2) (lon, lat): radians (haversine) or degrees; null in cell mode
-    const int32_t* qcell;            // (B), cell mode
     int64_t B, groups;
     int32_t G, C;
-    double thr;                      // radius
-    const double* red_k;             // (B), knn
-    const int64_t* j_last;           // (B), knn
-    double pc, cpc;                  // cell: pseudo_count and num_classes * pseudo_count
     const void* img;                 // (B, C) float32 / float64 or null
     int32_t img_kind;
     const int32_t* labels;           // (B), with greater / tied / argmax
     int32_t *greater, *tied, *argmax;
     double* prior;                   // (B, C) or null
-    int32_t* counts;                 // (B, C) or null
-    int32_t* ws;                     // chunks > 1: (chunks, groups, G * C) partial count rows
     int32_t chunks;                  // fold: how many
+};
+
+struct NeighborArgs : NeighborScanArgs {
+    const int32_t* qcell;            // (B), cell mode
+    double thr;                      // radius
+    const double* red_k;             // (B), knn
+    const int64_t* j_last;           // (B), knn
+    double pc, cpc;                  // cell: pseudo_count and num_classes * pseudo_count
+    int32_t *raw, *ws;               // the votes
 };
 
 struct NeighborSelectArgs {
@@ -145,42 +151,6 @@ __global__ __launch_bounds__(NEIGHBOR_BLOCK) void neighbor_prep_kernel(const dou
     }
 }
 
-// the parameters of the group's queries b0 .. b0 + live - 1 into LDS; the rows beyond B never have a member
-template <int MODE, bool HAV>
-__device__ __forceinline__ void neighbor_load_queries(const NeighborArgs& a, NeighborQuery* qs, int64_t b0, int live) {
-    const int t = threadIdx.x;
-    if (t < a.G) {
-        NeighborQuery q;
-        q.lat = q.lon = q.thr = __builtin_nan("");
-        q.cs = 0.0;
-        q.j_last = -1;
-        q.cell = NEIGHBOR_CELL_UNIFORM;
-        q.pad = 0;
-        if (t < live) {
-            if (MODE == NEIGHBOR_CELL) {
-                q.cell = a.qcell[b0 + t];
-            } else {
-                q.lon = a.q[2 * (b0 + t)];
-                q.lat = a.q[2 * (b0 + t) + 1];
-                q.cs = HAV ? cos(q.lat) : 0.0;
-                q.thr = MODE == NEIGHBOR_RADIUS ? a.thr : a.red_k[b0 + t];
-                if (MODE == NEIGHBOR_KNN) q.j_last = a.j_last[b0 + t];
-            }
-        }
-        qs[t] = q;
-    }
-}
-
-template <int MODE, bool HAV>
-__device__ __forceinline__ bool neighbor_member(const NeighborQuery& q, const NeighborPoint& p, int64_t j) {
-    if (MODE == NEIGHBOR_CELL) return p.cell == q.cell;
-    const double red = neighbor_red<HAV>(q.lon, q.lat, q.cs, p.lon, p.lat, p.cs);
-    if (MODE == NEIGHBOR_RADIUS) return red <= q.thr;
-    const double rk = q.thr;
-    if (rk != rk) return red == red;                       // fewer than k pairs with a number: all of them
-    return red < rk || (red == rk && j <= q.j_last);
-}
-
 // the three integers of row b by one wave: the scores are img[b, c] * prior_at(c) (prior_at(c) without image
 // predictions), the rule csp_rank_kernel.h's.  Shared by the count priors here and the KDE prior (kde_kernel.h).
 template <class PriorAt>
@@ -220,31 +190,33 @@ __device__ __forceinline__ void neighbor_rank_row(const void* img, int32_t img_k
     }
 }
 
-// the rows of a group, a wave each (rows wave, wave + 16, ...): counts / priors on request, the three integers
-template <int MODE>
-__device__ __forceinline__ void neighbor_rank_group(const NeighborArgs& a, const int32_t* counts, const NeighborQuery* qs,
-                                                    int64_t b0, int live) {
+// ---- the scan, the fold and the ranks of a group over a row policy P:
+//   P::Entry, P::Query (NEIGHBOR_QUERY_LDS bytes), P::Args (NeighborScanArgs and Entry *raw, *ws)
+//   P::stage(a, q, b, live)       the record of query b for the scan; !live: a row beyond B, which never has a member
+//   P::stage_fold(a, q, b, live)  what of it the ranks read
+//   P::member(a, q, p, j, row)    the predicate of point j and the one LDS add to row[p.cls]
+//   P::prior_of(a, q, row, lane)  the row's reduction by one wave; returns entry -> prior
+
+// the LDS of a workgroup: the rows, rounded up to 16 bytes, then the G records
+template <class Entry>
+__device__ __forceinline__ size_t neighbor_query_offset(int row_entries) {
+    return ((size_t)row_entries * sizeof(Entry) + 15) & ~(size_t)15;
+}
+
+// the rows of a group, a wave each (rows wave, wave + 16, ...): raw rows / priors on request, the three integers
+template <class P>
+__device__ __forceinline__ void neighbor_rank_group(const typename P::Args& a, const typename P::Entry* rows,
+                                                    const typename P::Query* qs, int64_t b0, int live) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int C = a.C;
     for (int g = wave; g < live; g += NEIGHBOR_VOTE_BLOCK / 64) {
-        const int32_t* const row = counts + (size_t)g * C;
+        const typename P::Entry* const row = rows + (size_t)g * C;
         const int64_t b = b0 + g;
-        int32_t n = 0;
-        for (int c = lane; c < C; c += 64) n += row[c];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) n += __shfl_xor(n, o);
-        const bool uniform = MODE == NEIGHBOR_CELL && qs[g].cell == NEIGHBOR_CELL_UNIFORM;
-        const double den = MODE == NEIGHBOR_CELL ? ((double)n + a.cpc) - (double)C : (double)((int64_t)C + (int64_t)n);
-        const double pc = a.pc, one_c = 1.0 / (double)C;
-        const auto prior_of = [&](int32_t cnt) {
-            if (uniform) return one_c;
-            if (MODE == NEIGHBOR_CELL) return (((double)cnt + pc) - 1.0) / den;
-            return (1.0 + (double)cnt) / den;
-        };
-        if (a.counts)
-            for (int c = lane; c < C; c += 64) a.counts[b * C + c] = row[c];
+        const auto prior_of = P::prior_of(a, qs[g], row, lane);
+        if (a.raw)
+            for (int c = lane; c < C; c += 64) a.raw[b * C + c] = row[c];
         if (a.prior)
             for (int c = lane; c < C; c += 64) a.prior[b * C + c] = prior_of(row[c]);
         if (!a.greater) continue;
@@ -252,23 +224,24 @@ __device__ __forceinline__ void neighbor_rank_group(const NeighborArgs& a, const
     }
 }
 
-template <int MODE, bool HAV>
-__global__ __launch_bounds__(NEIGHBOR_VOTE_BLOCK) void neighbor_vote_kernel(NeighborArgs a) {
-    extern __shared__ __attribute__((aligned(16))) int32_t nb_lds[];
+template <class P>
+__device__ __forceinline__ void neighbor_vote_body(const typename P::Args& a) {
+    using Entry = typename P::Entry;
+    extern __shared__ __attribute__((aligned(16))) unsigned char neighbor_lds[];
     const int t = threadIdx.x;
     const int G = a.G, C = a.C;
-    const int row_ints = G * C;                                   // at most NEIGHBOR_COUNT_LDS / 4
-    int32_t* const counts = nb_lds;
-    NeighborQuery* const qs = reinterpret_cast<NeighborQuery*>(nb_lds + ((row_ints + 3) & ~3));
+    const int row_entries = G * C;                                // at most NEIGHBOR_COUNT_LDS / sizeof(Entry)
+    Entry* const rows = reinterpret_cast<Entry*>(neighbor_lds);
+    typename P::Query* const qs = reinterpret_cast<typename P::Query*>(neighbor_lds + neighbor_query_offset<Entry>(row_entries));
     for (int64_t grp = blockIdx.x; grp < a.groups; grp += gridDim.x) {
         const int64_t b0 = grp * G;
         const int live = a.B - b0 < G ? (int)(a.B - b0) : G;
         __syncthreads();                                          // the last group's rows have been read
-        for (int i = t; i < row_ints; i += NEIGHBOR_VOTE_BLOCK) counts[i] = 0;
-        neighbor_load_queries<MODE, HAV>(a, qs, b0, live);
+        for (int i = t; i < row_entries; i += NEIGHBOR_VOTE_BLOCK) rows[i] = 0;
+        if (t < G) P::stage(a, qs[t], b0 + t, t < live);
         __syncthreads();
         // The workgroup is NEIGHBOR_VOTE_BLOCK threads: NEIGHBOR_VOTE_SUBS tiles of NEIGHBOR_BLOCK points side by side,
-        // NEIGHBOR_UNROLL such trips' loads issued together.  The count rows leave room for one workgroup a CU at the
+        // NEIGHBOR_UNROLL such trips' loads issued together.  The rows leave room for one workgroup a CU at the
         // widest rows: four waves a SIMD of ONE workgroup hide the latency of the float64 chains, four workgroups of
         // 256 would need four times the rows.
         const int sub = t / NEIGHBOR_BLOCK, tt = t % NEIGHBOR_BLOCK;
@@ -284,47 +257,119 @@ __global__ __launch_bounds__(NEIGHBOR_VOTE_BLOCK) void neighbor_vote_kernel(Neig
 #pragma unroll
             for (int u = 0; u < NEIGHBOR_UNROLL; ++u) {
                 if (j[u] < a.N) {
-                    for (int g = 0; g < live; ++g)
-                        if (neighbor_member<MODE, HAV>(qs[g], p[u], j[u])) atomicAdd(&counts[g * C + p[u].cls], 1);
+                    for (int g = 0; g < live; ++g) P::member(a, qs[g], p[u], j[u], rows + g * C);
                 }
             }
         }
         __syncthreads();
         if (gridDim.y > 1) {
-            int32_t* const out = a.ws + ((int64_t)blockIdx.y * a.groups + grp) * row_ints;
-            for (int i = t; i < row_ints; i += NEIGHBOR_VOTE_BLOCK) out[i] = counts[i];
+            Entry* const out = a.ws + ((int64_t)blockIdx.y * a.groups + grp) * row_entries;
+            for (int i = t; i < row_entries; i += NEIGHBOR_VOTE_BLOCK) out[i] = rows[i];
         } else {
-            neighbor_rank_group<MODE>(a, counts, qs, b0, live);
+            neighbor_rank_group<P>(a, rows, qs, b0, live);
         }
     }
 }
 
-// the chunks' partial count rows of a group, added in LDS, then ranked as the unsplit scan ranks them
-template <int MODE>
-__global__ __launch_bounds__(NEIGHBOR_VOTE_BLOCK) void neighbor_fold_kernel(NeighborArgs a) {
-    extern __shared__ __attribute__((aligned(16))) int32_t nb_lds[];
+// the chunks' partial rows of a group, added in LDS, then ranked as the unsplit scan ranks them
+template <class P>
+__device__ __forceinline__ void neighbor_fold_body(const typename P::Args& a) {
+    using Entry = typename P::Entry;
+    extern __shared__ __attribute__((aligned(16))) unsigned char neighbor_lds[];
     const int t = threadIdx.x;
     const int G = a.G, C = a.C;
-    const int row_ints = G * C;
-    int32_t* const counts = nb_lds;
-    NeighborQuery* const qs = reinterpret_cast<NeighborQuery*>(nb_lds + ((row_ints + 3) & ~3));
+    const int row_entries = G * C;
+    Entry* const rows = reinterpret_cast<Entry*>(neighbor_lds);
+    typename P::Query* const qs = reinterpret_cast<typename P::Query*>(neighbor_lds + neighbor_query_offset<Entry>(row_entries));
     for (int64_t grp = blockIdx.x; grp < a.groups; grp += gridDim.x) {
         const int64_t b0 = grp * G;
         const int live = a.B - b0 < G ? (int)(a.B - b0) : G;
         __syncthreads();
-        for (int i = t; i < row_ints; i += NEIGHBOR_VOTE_BLOCK) {
-            int32_t n = 0;
-            for (int y = 0; y < a.chunks; ++y) n += a.ws[((int64_t)y * a.groups + grp) * row_ints + i];
-            counts[i] = n;
+        for (int i = t; i < row_entries; i += NEIGHBOR_VOTE_BLOCK) {
+            Entry n = 0;
+            for (int y = 0; y < a.chunks; ++y) n += a.ws[((int64_t)y * a.groups + grp) * row_entries + i];
+            rows[i] = n;
         }
-        if (t < G) {                     // (the ranks read the cell alone)
-            NeighborQuery q{};
-            q.cell = MODE == NEIGHBOR_CELL && t < live ? a.qcell[b0 + t] : NEIGHBOR_CELL_UNIFORM;
-            qs[t] = q;
-        }
+        if (t < G) P::stage_fold(a, qs[t], b0 + t, t < live);
         __syncthreads();
-        neighbor_rank_group<MODE>(a, counts, qs, b0, live);
+        neighbor_rank_group<P>(a, rows, qs, b0, live);
     }
+}
+
+// ---- the count rows: int32 votes by predicate MODE under metric HAV (the fold and the ranks read MODE alone)
+template <int MODE, bool HAV>
+struct NeighborCountRows {
+    using Entry = int32_t;
+    using Query = NeighborQuery;
+    using Args = NeighborArgs;
+
+    static __device__ __forceinline__ void stage(const Args& a, Query& out, int64_t b, bool live) {
+        Query q;
+        q.lat = q.lon = q.thr = __builtin_nan("");
+        q.cs = 0.0;
+        q.j_last = -1;
+        q.cell = NEIGHBOR_CELL_UNIFORM;
+        q.pad = 0;
+        if (live) {
+            if (MODE == NEIGHBOR_CELL) {
+                q.cell = a.qcell[b];
+            } else {
+                q.lon = a.q[2 * b];
+                q.lat = a.q[2 * b + 1];
+                q.cs = HAV ? cos(q.lat) : 0.0;
+                q.thr = MODE == NEIGHBOR_RADIUS ? a.thr : a.red_k[b];
+                if (MODE == NEIGHBOR_KNN) q.j_last = a.j_last[b];
+            }
+        }
+        out = q;
+    }
+
+    static __device__ __forceinline__ void stage_fold(const Args& a, Query& out, int64_t b, bool live) {
+        Query q{};                       // (the ranks read the cell alone)
+        q.cell = MODE == NEIGHBOR_CELL && live ? a.qcell[b] : NEIGHBOR_CELL_UNIFORM;
+        out = q;
+    }
+
+    static __device__ __forceinline__ void member(const Args&, const Query& q, const NeighborPoint& p, int64_t j, Entry* row) {
+        bool in;
+        if (MODE == NEIGHBOR_CELL) {
+            in = p.cell == q.cell;
+        } else {
+            const double red = neighbor_red<HAV>(q.lon, q.lat, q.cs, p.lon, p.lat, p.cs);
+            const double rk = q.thr;
+            if (MODE == NEIGHBOR_RADIUS) in = red <= rk;
+            else if (rk != rk) in = red == red;                   // fewer than k pairs with a number: all of them
+            else in = red < rk || (red == rk && j <= q.j_last);
+        }
+        if (in) atomicAdd(&row[p.cls], 1);
+    }
+
+    static __device__ __forceinline__ auto prior_of(const Args& a, const Query& q, const Entry* row, int lane) {
+#pragma clang fp contract(off)
+        const int C = a.C;
+        int32_t n = 0;
+        for (int c = lane; c < C; c += 64) n += row[c];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) n += __shfl_xor(n, o);
+        const bool uniform = MODE == NEIGHBOR_CELL && q.cell == NEIGHBOR_CELL_UNIFORM;
+        const double den = MODE == NEIGHBOR_CELL ? ((double)n + a.cpc) - (double)C : (double)((int64_t)C + (int64_t)n);
+        const double pc = a.pc, one_c = 1.0 / (double)C;
+        return [=](int32_t cnt) {
+            if (uniform) return one_c;
+            if (MODE == NEIGHBOR_CELL) return (((double)cnt + pc) - 1.0) / den;
+            return (1.0 + (double)cnt) / den;
+        };
+    }
+};
+
+template <int MODE, bool HAV>
+__global__ __launch_bounds__(NEIGHBOR_VOTE_BLOCK) void neighbor_vote_kernel(NeighborArgs a) {
+    neighbor_vote_body<NeighborCountRows<MODE, HAV>>(a);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(NEIGHBOR_VOTE_BLOCK) void neighbor_fold_kernel(NeighborArgs a) {
+    neighbor_fold_body<NeighborCountRows<MODE, false>>(a);
 }
 
 template <bool HAV>

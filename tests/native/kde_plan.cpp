@@ -3,53 +3,11 @@
 // query groups and the tiles of bins cover every (query, bin) pair exactly once, LDS and workspace sizes at the class
 // edges (1, 8142, 16384; 16385 refused), B = 1, M = 1, forced chunks, a capped grid, the scale bits up to a total
 // count of 2^31 - 1 - no row can reach 2^62 -, and the refusals.
-#include <cstdint>
-#include <cstdio>
 #include <limits>
-#include <vector>
 
-#include "../../range_amd/csrc/host_plan.h"
+#include "plan_cover.h"
 
 using namespace range_host;
-
-#define CHECK(cond)                                                           \
-    do {                                                                      \
-        if (!(cond)) {                                                        \
-            std::printf("FAILED line %d: %s\n", __LINE__, #cond);             \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
-
-// the kernel's walk (kde_kernel.h) on the host: how often query i / bin j is visited
-static int check_cover(const KdePlan& p, int64_t B, int64_t M) {
-    if (B <= (1 << 16)) {
-        std::vector<int> seen((size_t)B, 0);
-        int64_t groups = 0;
-        for (int64_t x = 0; x < (int64_t)p.grid; ++x) {
-            CHECK(p.groups_of(x) >= 1);
-            groups += p.groups_of(x);
-            for (int64_t grp = x; grp < p.groups; grp += p.grid)
-                for (int g = 0; g < p.group; ++g)
-                    if (grp * p.group + g < B) seen[(size_t)(grp * p.group + g)] += 1;
-        }
-        CHECK(groups == p.groups);
-        for (int v : seen) CHECK(v == 1);
-    }
-    if (M <= (1 << 20)) {
-        std::vector<int> seen((size_t)M, 0);
-        int64_t tiles = 0;
-        for (int y = 0; y < p.chunks; ++y) {
-            CHECK(p.tiles_of(y) >= 1);          // no chunk is empty: every partial row of the workspace is written
-            tiles += p.tiles_of(y);
-            for (int64_t tile = y; tile < p.n_tiles; tile += p.chunks)
-                for (int t = 0; t < p.block; ++t)
-                    if (tile * p.block + t < M) seen[(size_t)(tile * p.block + t)] += 1;
-        }
-        CHECK(tiles == p.n_tiles);
-        for (int v : seen) CHECK(v == 1);
-    }
-    return 0;
-}
 
 int main() {
     const int T = NEIGHBOR_BLOCK;
@@ -94,7 +52,7 @@ int main() {
                             // uint64 rows, 16-byte aligned, then the queries' parameters: inside the CU's 160 KB
                             CHECK(p.lds_bytes >= (size_t)G * C * 8 + (size_t)G * NEIGHBOR_QUERY_LDS && p.lds_bytes <= 160 * 1024);
                             CHECK(((p.lds_bytes - (size_t)G * NEIGHBOR_QUERY_LDS) % 16) == 0);
-                            // the kernel's own offset of the parameters: the rows rounded up to an even number of words
+                            // the kernel's own offset of the parameters (neighbor_query_offset): the rows rounded up to 16 bytes, two words
                             CHECK((size_t)(((int64_t)G * C + 1) & ~INT64_C(1)) * 8 + (size_t)G * NEIGHBOR_QUERY_LDS == p.lds_bytes);
                             if (p.chunks == 1) {
                                 CHECK(p.ws_ints == 0 && p.ws_bytes == 0 && p.fold_grid == 0);

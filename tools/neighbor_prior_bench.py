@@ -28,6 +28,7 @@ import torch
 
 from range_amd import _neighbors_native as nn
 from range_amd import geo_baselines as gb
+from prior_bench_common import blobs, timed
 
 
 def opt(name, default):
@@ -42,40 +43,12 @@ HP["num_neighbors"] = min(HP["num_neighbors"], N)
 DEV = torch.device("cuda:0")
 
 
-def blobs(n, seed, centres=None):
-    """Points around 40 'land' centres, denser where a centre is heavier; classes correlate with the centre."""
-    rng = np.random.default_rng(seed)
-    if centres is None:
-        centres = np.stack([rng.uniform(-160, 160, 40), rng.uniform(-50, 65, 40), rng.uniform(2, 12, 40), rng.random(40) ** 2 + 0.05], 1)
-    w = centres[:, 3] / centres[:, 3].sum()
-    which = rng.choice(len(centres), n, p=w)
-    pts = centres[which, :2] + rng.normal(0, 1, (n, 2)) * centres[which, 2:3]
-    pts[:, 0] = np.clip(pts[:, 0], -179.99, 179.99)
-    pts[:, 1] = np.clip(pts[:, 1], -89.99, 89.99)
-    cls = (which * (C // len(centres)) + rng.integers(0, max(1, C // 8), n)) % C
-    return pts, cls, centres
-
-
-def timed(fn, repeats):
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b) * 1e-3)
-    return float(np.median(times))
-
-
 def stage(name, seconds, scans=1, **more):
     return dict(stage=name, seconds=round(seconds, 5), scans=scans, pairs_per_s=float(f"{B * N / seconds:.4g}"), **more)
 
 
-train, train_cls, centres = blobs(N, 1)
-query, _, _ = blobs(B, 2, centres)
+train, train_cls, centres = blobs(N, 1, C)
+query, _, _ = blobs(B, 2, C, centres)
 labels = torch.from_numpy(np.random.default_rng(3).integers(0, C, B).astype(np.int32)).to(DEV)
 img = torch.rand((B, C), dtype=torch.float32, device=DEV)
 out = {"train": N, "queries": B, "classes": C, "pairs": B * N, "hyper_params": HP, "repeats": REPEATS, "plan": nn.plan(B, N, C, HP["num_neighbors"])}
