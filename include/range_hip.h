@@ -524,6 +524,8 @@ int range_finalize(range_ctx* ctx, const float* partials_dev, int32_t n_parts,
  * Replaces LocationEncoder.forward for 'RANGE' / 'RANGE+' (range/range.py:206-240) up to the
  * final device->host copy, which stays in the Python shim.
  *   model : RANGE_MODEL_RANGE (tau 15) | RANGE_MODEL_RANGE_PLUS (tau 12 / 40, beta blend)
+ *   beta : in [0,1] for RANGE_MODEL_RANGE_PLUS (RANGE_ERR_INVALID otherwise, at every batch size, before anything
+ *          is enqueued); ignored for RANGE_MODEL_RANGE
  *   out_dev : (B,1280) float64
  * A batch of several rounds of pass 2 against a bank beyond the stream-K walk (exact w @ V, temperatures
  * up to RANGE_MAX_TAU, logits kept) runs in chunks of query tiles: pass 1 of chunk i + 1 on a second,

@@ -106,7 +106,8 @@ int range_set_pv_mode(range_ctx* c, int32_t mode) {
     if (mode != RANGE_PV_EXACT && mode != RANGE_PV_BF16X3) return fail(RANGE_ERR_INVALID, "unknown pv mode %d", mode);
     ENTER_DEVICE(c);
     c->bank.pv_mode = mode;
-    if (mode == RANGE_PV_BF16X3 && c->bank.has_bank && c->bank.vplanes_groups == 0) return build_vplanes(c);
+    // (a keys-only bank has no values to split: the next range_set_bank builds the planes)
+    if (mode == RANGE_PV_BF16X3 && c->bank.has_bank && c->bank.has_values && c->bank.vplanes_groups == 0) return build_vplanes(c);
     return RANGE_OK;
 }
 int32_t range_get_pv_mode(const range_ctx* c) { return c ? c->bank.pv_mode : -1; }

@@ -16,6 +16,8 @@ static int model_params(const range_ctx* c, int32_t model, float beta, ModelPara
     if (c->tau_sem_set > 0.f) m.tau_sem = c->tau_sem_set;
     if (c->tau_geo_set > 0.f && model == RANGE_MODEL_RANGE_PLUS) m.tau_geo = c->tau_geo_set;
     m.beta = model == RANGE_MODEL_RANGE ? 1.0f : beta;
+    // (here, not only in pass 2: the one-pass route of up to 32 queries never gets there)
+    if (!(m.beta >= 0.f && m.beta <= 1.f)) return fail(RANGE_ERR_INVALID, "beta must be in [0,1]");
     return RANGE_OK;
 }
 
