@@ -149,6 +149,14 @@ struct range_ctx {
         DevBuf<double> ws_redk;
         DevBuf<int64_t> ws_jlast;
     } nb;
+    // range_headfit_begin: the class head being fitted (headfit_kernels.h) - W and Adam's moments in the packed
+    // layout of csp_pack_head, the steps taken, the workspace of a step (host_plan.h: headfit_plan)
+    struct Headfit {
+        int C = 0, F = 0;                // C == 0: no fit begun
+        int64_t steps = 0;
+        DevBuf<float> d_w, d_m, d_v;
+        DevBuf<float> ws;
+    } hf;
     // words of host memory the kernels can write (hipHostMallocMapped; async_err.h): set by a persistent
     // kernel whose bounded wait for other workgroups gave up; read - without synchronising - by the
     // next call and behind every synchronising exit (check_async_error)

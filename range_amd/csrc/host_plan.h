@@ -1370,4 +1370,84 @@ inline bool cluster_cut(int64_t n, const int32_t* merges, const double* heights,
     return true;
 }
 
+// The fit of the CSP class head from frozen embeddings (headfit_kernels.h; include/range_headfit.h): one step of the
+// reference's supervised stage on `rows` = B + Bg gathered rows - the batch's, then the background's - as, per PANEL
+// of whole 32-class tiles, the logit gradient G (rows x panel_cols, the head's tile and chunks: csp_head_plan), a
+// fold of the tiles' per-row loss sums, and dW = G^T X with Adam behind it.  The panel is the widest that keeps
+// the workspace - the gathered X, G, the panel's per-tile row sums (two kinds), the running row sums - within
+// HEADFIT_MAX_WS.  An item of the gradient launch is (row tile, chunk of the panel), of the update (class tile,
+// group of HEADFIT_FGROUP features: four waves of two 32-feature tiles); both are walked grid-stride.
+constexpr int64_t HEADFIT_MAX_ROWS = 8192;
+constexpr size_t HEADFIT_MAX_WS = (size_t)256 << 20;
+constexpr int HEADFIT_FGROUP = 256;
+
+struct HeadfitPlan {
+    bool valid = false;
+    const char* why = "";
+    int C = 0, F = 0;
+    int64_t rows = 0, row_tiles = 0, max_grid = 0;
+    int m_tiles = 0, tile_rows = 0, ld = 0, k_groups = 0, n_tiles = 0, wave_tiles = 0, cols_per_pass = 0;
+    int panel_cols = 0, panel_tiles = 0, n_panels = 0, f_groups = 0;
+    size_t lds_bytes = 0, packed_floats = 0;
+    size_t x_floats = 0, g_floats = 0, part_floats = 0, rowsum_floats = 0, ws_bytes = 0;   // the workspace, in this order
+    unsigned row_grid = 0;               // of the per-row kernels (fold)
+    unsigned gather_grid = 0, unpack_grid = 0;
+    int block = CSP_BLOCK;
+    unsigned cap(int64_t items) const { return (unsigned)std::min(items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID); }
+    // panel p: its first class tile, its tiles
+    int panel_first_tile(int p) const { return p * panel_tiles; }
+    int panel_n_tiles(int p) const { return std::min(panel_tiles, n_tiles - p * panel_tiles); }
+    // the gradient launch of panel p: chunks of cols_per_pass columns, items = row tiles x chunks
+    int grad_chunks(int p) const { return (panel_n_tiles(p) + 4 * wave_tiles - 1) / (4 * wave_tiles); }
+    int64_t grad_items(int p) const { return row_tiles * grad_chunks(p); }
+    unsigned grad_grid(int p) const { return cap(grad_items(p)); }
+    void grad_item(int p, int64_t it, int64_t& row_tile, int& chunk) const {
+        row_tile = it / grad_chunks(p);
+        chunk = (int)(it - row_tile * grad_chunks(p));
+    }
+    // the local tiles wave `w` computes in chunk `ch` of panel p: the first, and how many (stride 4)
+    int wave_first_tile(int ch, int w) const { return ch * 4 * wave_tiles + w; }
+    int wave_n_tiles(int p, int ch, int w) const {
+        const int t0 = wave_first_tile(ch, w), n = panel_n_tiles(p);
+        return n > t0 ? std::min(wave_tiles, (n - t0 + 3) / 4) : 0;
+    }
+    // the update launch of panel p: items = class tiles x feature groups
+    int64_t update_items(int p) const { return (int64_t)panel_n_tiles(p) * f_groups; }
+    unsigned update_grid(int p) const { return cap(update_items(p)); }
+};
+
+// panel_cols: 0, or a narrower panel than the workspace allows (rounded up to whole tiles) - for tests
+inline HeadfitPlan headfit_plan(int C, int F, int64_t rows, int64_t max_grid = 0, int panel_cols = 0) {
+    HeadfitPlan p;
+    if (F < 1 || F > CSP_MAX_WIDTH) { p.why = "feature width outside 1 .. 1024"; return p; }
+    if (C < 1 || C > CSP_MAX_CLASSES) { p.why = "num_classes outside 1 .. 32768"; return p; }
+    if (rows < 1 || rows > HEADFIT_MAX_ROWS) { p.why = "B + Bg outside 1 .. 8192"; return p; }
+    if (max_grid < 0 || panel_cols < 0) { p.why = "max_grid and panel_cols must be >= 0"; return p; }
+    const CspHeadPlan h = csp_head_plan(F, C, C, rows, CSP_HEAD_PROBS);
+    p.C = C; p.F = F; p.rows = rows; p.max_grid = max_grid;
+    p.m_tiles = h.m_tiles; p.tile_rows = h.tile_rows; p.ld = h.ld; p.k_groups = h.k_groups; p.n_tiles = h.n_tiles;
+    p.wave_tiles = h.wave_tiles; p.cols_per_pass = h.cols_per_pass; p.row_tiles = h.row_tiles;
+    p.packed_floats = h.packed_floats;
+    // X tile, and the labels of its rows
+    p.lds_bytes = ((size_t)p.tile_rows * p.ld + (size_t)p.tile_rows) * sizeof(float);
+    p.x_floats = (size_t)rows * F;
+    p.rowsum_floats = 2 * (size_t)rows;
+    // a tile of the panel costs 32 columns of G and two row sums per row
+    const size_t fixed = (p.x_floats + p.rowsum_floats) * sizeof(float), per_tile = (size_t)rows * (CSP_NTILE + 2) * sizeof(float);
+    int tiles = (int)std::min<size_t>((HEADFIT_MAX_WS - fixed) / per_tile, (size_t)p.n_tiles);
+    if (panel_cols) tiles = std::min(tiles, (panel_cols + CSP_NTILE - 1) / CSP_NTILE);
+    p.panel_tiles = tiles;
+    p.panel_cols = tiles * CSP_NTILE;
+    p.n_panels = (p.n_tiles + tiles - 1) / tiles;
+    p.g_floats = (size_t)rows * p.panel_cols;
+    p.part_floats = 2 * (size_t)tiles * rows;
+    p.ws_bytes = (p.x_floats + p.g_floats + p.part_floats + p.rowsum_floats) * sizeof(float);
+    p.f_groups = (F + HEADFIT_FGROUP - 1) / HEADFIT_FGROUP;
+    p.row_grid = p.cap((rows + CSP_BLOCK - 1) / CSP_BLOCK);
+    p.gather_grid = p.cap(((int64_t)p.x_floats + CSP_BLOCK - 1) / CSP_BLOCK);
+    p.unpack_grid = p.cap(((int64_t)C * F + CSP_BLOCK - 1) / CSP_BLOCK);
+    p.valid = true;
+    return p;
+}
+
 }  // namespace range_host

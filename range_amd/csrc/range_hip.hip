@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/range_hip.h"
+#include "../../include/range_headfit.h"
 #include "host_common.h"
 #include "host_copy.h"
 #include "host_plan.h"
@@ -33,6 +34,7 @@
 #include "csp_kernel.h"
 #include "csp_head_kernel.h"
 #include "csp_rank_kernel.h"
+#include "headfit_kernels.h"
 #include "checker_kernel.h"
 #include "neighbor_kernel.h"
 #include "kde_kernel.h"
@@ -50,6 +52,7 @@ using namespace range_host;
 // ... and the side encoders'
 #include "posenc_host.h"
 #include "csp_host.h"
+#include "headfit_host.h"
 #include "checker_host.h"
 #include "neighbor_host.h"
 #include "kde_host.h"

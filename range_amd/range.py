@@ -388,6 +388,28 @@ class CspLocationModel(nn.Module):
             engine.set_csp_head(p.class_emb)
         self.eval()
 
+    def set_class_head(self, weight) -> None:
+        """Install a class head - a fitted one (range_amd.head_fit) - behind the network: ``weight`` (num_classes,
+        num_filts) float32, numpy or torch, finite.  It goes through the engine's ``set_csp_head`` like a checkpoint's,
+        ``num_classes`` is set and ``loc_enc.class_emb.weight`` joins (or replaces) the mirror parameters, so that
+        ``forward(return_feats=False)``, ``eval_single_class``, ``class_sum``, ``label_ranks``, ``GridPredictor`` and
+        ``compute_acc_batch`` work on a model loaded without ``class_head=True``."""
+        w = weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)
+        if w.dtype != np.float32 or w.ndim != 2 or w.shape[1] != self.loc_emb_dim:
+            raise ValueError(f"class head: float32 (num_classes, {self.loc_emb_dim}), got {w.dtype} {w.shape}")
+        if not 1 <= w.shape[0] <= 32768:
+            raise ValueError(f"class head: num_classes={w.shape[0]}: 1 .. 32768 are supported")
+        if not np.isfinite(w).all():
+            raise ValueError("class head: non-finite weights")
+        w = np.ascontiguousarray(w)
+        eng = self._engine[0]
+        eng.set_csp_head(w)
+        enc = self.loc_enc
+        enc.class_emb = nn.Linear(self.loc_emb_dim, w.shape[0], bias=False, device="meta")
+        enc.class_emb.weight = nn.Parameter(torch.as_tensor(w, dtype=torch.float32, device=eng.device), requires_grad=False)
+        enc.num_classes = w.shape[0]
+        self.num_classes = w.shape[0]
+
     def _need_head(self, what: str):
         if not self.num_classes:
             raise NotImplementedError(f"CSP: {what} needs the class head - load_model(..., class_head=True); without it "
