@@ -52,6 +52,7 @@ class CspParams:
     ln_beta: List[Optional[np.ndarray]]
     num_classes: int = 0                     # read_csp_checkpoint(class_head=True): params['num_classes']
     class_emb: Optional[np.ndarray] = None   # ... and float32 (num_classes, num_filts), bias-free
+    dropout: float = 0.0                     # params['dropout']: train mode only (range_amd.csp_fit)
 
     @property
     def input_dim(self) -> int:
@@ -127,6 +128,7 @@ def read_csp_checkpoint(path: str, class_head: bool = False) -> CspParams:
         raise ValueError("state_dict has more layers than params['num_hidden_layer'] says")
     p = CspParams(spa, kind, F, float(params["min_radius"]), float(params["max_radius"]), freq_init, freqs,
                   n_hidden, hidden, num_filts, act, use_layn, skip, widths, ws, bs, gs, bes)
+    p.dropout = float(params.get("dropout", 0.0))
     if class_head:
         C = int(params["num_classes"])
         if not 1 <= C <= MAX_CLASSES:
@@ -138,3 +140,42 @@ def read_csp_checkpoint(path: str, class_head: bool = False) -> CspParams:
         p.num_classes = C
         p.class_emb = _np32(sd[_CLASS_EMB + ".weight"], _CLASS_EMB + ".weight", (C, num_filts))
     return p
+
+
+def save_csp_checkpoint(path: str, p: CspParams) -> str:
+    """Write ``p`` - a trained network (range_amd.csp_fit) - as the ``{'params', 'state_dict'}`` file csp/main/trainer.py
+    saves, under the reference's key names (``loc_enc.spa_enc.ffn.layers.{i}.linear.*`` / ``.layernorm.*`` and their
+    ``spa_enc.*`` aliases, ``loc_enc.class_emb.weight`` / ``class_emb.weight`` when ``p.class_emb`` is set):
+    ``read_csp_checkpoint(path, class_head=p.class_emb is not None)`` returns the same tensors bit for bit.  ``params``
+    holds what the reader and the reference's ``get_model`` / ``get_ffn`` read of the network; the user head and the
+    image decoder, which a fit here does not train, are not written."""
+    import torch
+
+    if p.spa_enc_type not in SPA_ENC_KINDS or p.activation not in ACTIVATIONS:
+        raise NotImplementedError(f"CSP spa_enc_type={p.spa_enc_type!r} / spa_f_act={p.activation!r}")
+    n = len(p.widths)
+    if not (len(p.weights) == len(p.biases) == len(p.ln_gamma) == len(p.ln_beta) == n):
+        raise ValueError("one weight, bias, gamma and beta entry per layer")
+    sd = {}
+    d_in = p.input_dim
+    for i, d_out in enumerate(p.widths):
+        has_ln = p.use_layn and i + 1 < n
+        entries = [("linear.weight", p.weights[i], (d_out, d_in)), ("linear.bias", p.biases[i], (d_out,))]
+        if has_ln:
+            entries += [("layernorm.weight", p.ln_gamma[i], (d_out,)), ("layernorm.bias", p.ln_beta[i], (d_out,))]
+        for name, a, shape in entries:
+            t = torch.from_numpy(_np32(a, f"layer {i} {name}", shape).copy())
+            sd[f"{_PREFIX}{i}.{name}"] = t
+            sd[f"spa_enc.ffn.layers.{i}.{name}"] = t
+        d_in = d_out
+    params = {"spa_enc_type": p.spa_enc_type, "num_loc_feats": 2, "num_filts": int(p.num_filts), "num_users": 1,
+              "frequency_num": int(p.frequency_num), "max_radius": p.max_radius, "min_radius": p.min_radius,
+              "spa_f_act": p.activation, "freq_init": p.freq_init, "num_hidden_layer": int(p.num_hidden_layer),
+              "hidden_dim": int(p.hidden_dim), "dropout": float(p.dropout), "use_layn": bool(p.use_layn),
+              "skip_connection": bool(p.skip_connection), "device": "cpu", "num_classes": int(p.num_classes)}
+    if p.class_emb is not None:
+        t = torch.from_numpy(_np32(p.class_emb, _CLASS_EMB + ".weight", (p.num_classes, p.num_filts)).copy())
+        sd[_CLASS_EMB + ".weight"] = t
+        sd["class_emb.weight"] = t
+    torch.save({"params": params, "state_dict": sd}, path)
+    return path

@@ -157,6 +157,19 @@ struct range_ctx {
         DevBuf<float> d_w, d_m, d_v;
         DevBuf<float> ws;
     } hf;
+    // range_cspfit_begin: the CSP network being trained (cspfit_kernels.h) - every parameter and Adam's two moments at
+    // the offsets of host_plan.h: cspfit_plan, the frequencies, the steps taken, the workspace of a step
+    struct Cspfit {
+        int C = 0;                       // 0: no fit begun
+        int kind = 0, F = 0, act = 0, n_layers = 0;
+        bool skip = false, layn = false;
+        int widths[CSP_MAX_LAYERS] = {};
+        int64_t steps = 0;
+        size_t store = 0;                // floats of one copy: d_pmv holds the parameters, then m, then v
+        DevBuf<float> d_pmv;
+        DevBuf<double> d_freq;
+        DevBuf<float> ws;
+    } cf;
     // words of host memory the kernels can write (hipHostMallocMapped; async_err.h): set by a persistent
     // kernel whose bounded wait for other workgroups gave up; read - without synchronising - by the
     // next call and behind every synchronising exit (check_async_error)

@@ -6,6 +6,24 @@ enum { HEADFIT_STEP = 0, HEADFIT_GRAD = 1, HEADFIT_LOSS = 2 };
 
 struct HeadfitAdam { double lr, beta1, beta2, eps, weight_decay; };
 
+// torch.optim.Adam's scalars of the step behind `steps` taken ones, in double as Python computes them, into `u` - or
+// why the hyper-parameters are refused.  Shared with the CSP encoder fit (cspfit_host.h).
+static int headfit_adam_scalars(const HeadfitAdam& o, int64_t steps, HeadfitUpdateArgs& u) {
+    if (!(o.lr >= 0.0) || !(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0) || !(o.eps >= 0.0) ||
+        !(o.weight_decay >= 0.0) || !std::isfinite(o.lr) || !std::isfinite(o.eps) || !std::isfinite(o.weight_decay))
+        return fail(RANGE_ERR_INVALID, "Adam: lr, eps, weight_decay must be finite and >= 0, the betas in [0, 1)");
+    const double t = (double)(steps + 1);
+    const double bc1 = 1.0 - std::pow(o.beta1, t), bc2 = 1.0 - std::pow(o.beta2, t);
+    u.wd = (float)o.weight_decay;
+    u.omb1 = (float)(1.0 - o.beta1);
+    u.b2 = (float)o.beta2;
+    u.omb2 = (float)(1.0 - o.beta2);
+    u.eps = (float)o.eps;
+    u.step_size = (float)(o.lr / bc1);
+    u.bc2_sqrt = (float)std::sqrt(bc2);
+    return RANGE_OK;
+}
+
 static void (*headfit_grad_kernel_for(int m_tiles, bool write_g))(HeadfitGradArgs) {
     static void (*const kernels[2][2])(HeadfitGradArgs) = {{headfit_grad_kernel<1, false>, headfit_grad_kernel<1, true>},
                                                           {headfit_grad_kernel<2, false>, headfit_grad_kernel<2, true>}};
@@ -33,22 +51,8 @@ static int headfit_run(range_ctx* c, int what, const float* feats, int64_t N, co
     const HeadfitPlan p = headfit_plan(h.C, h.F, R, max_grid, panel_cols);
     if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %d, Bg = %d: %s", B, Bg, p.why);
     HeadfitUpdateArgs u{};
-    if (what == HEADFIT_STEP) {
-        const HeadfitAdam& o = *adam;
-        if (!(o.lr >= 0.0) || !(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0) || !(o.eps >= 0.0) ||
-            !(o.weight_decay >= 0.0) || !std::isfinite(o.lr) || !std::isfinite(o.eps) || !std::isfinite(o.weight_decay))
-            return fail(RANGE_ERR_INVALID, "Adam: lr, eps, weight_decay must be finite and >= 0, the betas in [0, 1)");
-        // torch.optim.Adam's scalars, in double as Python computes them
-        const double t = (double)(h.steps + 1);
-        const double bc1 = 1.0 - std::pow(o.beta1, t), bc2 = 1.0 - std::pow(o.beta2, t);
-        u.wd = (float)o.weight_decay;
-        u.omb1 = (float)(1.0 - o.beta1);
-        u.b2 = (float)o.beta2;
-        u.omb2 = (float)(1.0 - o.beta2);
-        u.eps = (float)o.eps;
-        u.step_size = (float)(o.lr / bc1);
-        u.bc2_sqrt = (float)std::sqrt(bc2);
-    }
+    if (what == HEADFIT_STEP)
+        if (int rc = headfit_adam_scalars(*adam, h.steps, u)) return rc;
     ENTER_DEVICE(c);
     if (h.ws.ensure(p.ws_bytes / sizeof(float)) != hipSuccess)
         return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of workspace)", p.ws_bytes);

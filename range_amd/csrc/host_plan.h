@@ -1450,4 +1450,107 @@ inline HeadfitPlan headfit_plan(int C, int F, int64_t rows, int64_t max_grid = 0
     return p;
 }
 
+
+// The fit of a whole CSP location encoder with its class head (cspfit_kernels.h; include/range_cspfit.h): one step of
+// the reference's supervised stage on `rows` = B + Bg locations, layer by layer.  Forward, per layer: Z = X W^T as the
+// class head's LOGITS launch (csp_head_plan with the layer's weight in the head's packed layout), then a row launch
+// (bias, activation, dropout, skip, LayerNorm - `lpr` = CSP_BLOCK / the encoder's tile rows lanes a row, the
+// encoder's own reduction order).  The head is headfit_plan on the embeddings, with dE = G W_c behind every
+// panel's logit gradient.  Backward, per layer from the last: a row launch (LayerNorm backward, skip, mask, act'),
+// the column sums (db, dgamma, dbeta; one thread a column, rows in order), dX = dZ W (an item: 32 rows x
+// CSPFIT_BACK_COLS columns, a wave one 32 x 32 tile) and dW = dZ^T X as the head fit's update launch.
+//
+// Stored parameters - the same offsets into the weights and Adam's two moments: per layer W in the head's packed
+// layout, b, gamma, beta (each padded to whole 32-column tiles; gamma / beta only behind a LayerNorm), then the
+// packed class_emb.  Unpacked order (range_cspfit_grad / _params): per layer W (out, in), b, gamma, beta, then
+// class_emb (C, num_filts).  Workspace: the features and every layer's output (a layer's input is the one before
+// it), every layer's pre-activation Z, two gradient images (ping-pong dY / dX), dZ, dY * xhat, then the head's G,
+// tile sums and row sums; at most CSPFIT_MAX_WS, or the shape is refused.
+constexpr size_t CSPFIT_MAX_WS = (size_t)512 << 20;
+constexpr int CSPFIT_BACK_COLS = 128;
+constexpr int CSPFIT_COLSUM_BLOCK = 64;
+
+struct CspfitPlan {
+    bool valid = false;
+    const char* why = "";
+    CspPlan net;                         // csp_plan of the network on `rows` locations: widths, live skips, LayerNorms
+    HeadfitPlan head;                    // the class head on (rows, num_filts)
+    int64_t rows = 0, max_grid = 0;
+    int C = 0, n_layers = 0, widest = 0, lpr = 0, rows_per_wg = 0;
+    size_t w_off[CSP_MAX_LAYERS] = {}, b_off[CSP_MAX_LAYERS] = {}, g_off[CSP_MAX_LAYERS] = {}, be_off[CSP_MAX_LAYERS] = {};
+    size_t c_off = 0, store_floats = 0;
+    size_t uw_off[CSP_MAX_LAYERS] = {}, ub_off[CSP_MAX_LAYERS] = {}, ug_off[CSP_MAX_LAYERS] = {}, ube_off[CSP_MAX_LAYERS] = {};
+    size_t uc_off = 0, n_params = 0;
+    size_t x_off[CSP_MAX_LAYERS + 1] = {}, z_off[CSP_MAX_LAYERS] = {};   // x_off[l]: layer l's input; [n_layers]: the embeddings
+    size_t dy_off[2] = {}, dz_off = 0, dyx_off = 0, g_ws_off = 0, part_off = 0, rowsum_off = 0, ws_floats = 0, ws_bytes = 0;
+    size_t lds_bytes = 0;                // the largest of the launches
+    unsigned feat_grid = 0, row_grid = 0;
+    int block = CSP_BLOCK;
+    unsigned cap(int64_t items) const { return (unsigned)std::min(items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID); }
+    int in(int l) const { return net.layer[l].in; }
+    int out(int l) const { return net.layer[l].out; }
+    // layer l's forward product: the head's LOGITS launch on (rows, in) x (out, in)^T
+    CspHeadPlan fwd(int l) const { return csp_head_plan(in(l), out(l), out(l), rows, CSP_HEAD_LOGITS, max_grid); }
+    // layer l's dW = dZ^T X: the head fit's update launch with `out` classes of `in` features (always one panel)
+    HeadfitPlan upd(int l) const { return headfit_plan(out(l), in(l), rows, max_grid); }
+    // dX = dZ W / dE = G W_c on `cols` output columns: items = 32-row tiles x groups of CSPFIT_BACK_COLS columns
+    int64_t back_row_tiles() const { return (rows + 31) / 32; }
+    int back_col_groups(int cols) const { return (cols + CSPFIT_BACK_COLS - 1) / CSPFIT_BACK_COLS; }
+    int64_t back_items(int cols) const { return back_row_tiles() * back_col_groups(cols); }
+    unsigned back_grid(int cols) const { return cap(back_items(cols)); }
+    // the column sums of layer l: one thread a (kind, column)
+    int colsum_kinds(int l) const { return net.layer[l].layn ? 3 : 1; }
+    unsigned colsum_grid(int l) const { return cap(((int64_t)colsum_kinds(l) * out(l) + CSPFIT_COLSUM_BLOCK - 1) / CSPFIT_COLSUM_BLOCK); }
+};
+
+inline CspfitPlan cspfit_plan(int kind, int F, int n_layers, const int* widths, bool skip, bool use_layn, int C, int64_t rows,
+                              int64_t max_grid = 0, int panel_cols = 0) {
+    CspfitPlan p;
+    if (rows < 1 || rows > HEADFIT_MAX_ROWS) { p.why = "B + Bg outside 1 .. 8192"; return p; }
+    if (max_grid < 0 || panel_cols < 0) { p.why = "max_grid and panel_cols must be >= 0"; return p; }
+    p.net = csp_plan(kind, F, n_layers, widths, skip, use_layn, rows, max_grid);
+    if (!p.net.valid) { p.why = p.net.why; return p; }
+    p.head = headfit_plan(C, p.net.out_width, rows, max_grid, panel_cols);
+    if (!p.head.valid) { p.why = p.head.why; return p; }
+    p.rows = rows; p.max_grid = max_grid; p.C = C; p.n_layers = n_layers;
+    p.lpr = CSP_BLOCK / p.net.tile_rows;
+    p.rows_per_wg = p.net.tile_rows;
+    size_t off = 0, uoff = 0, ws = 0;
+    p.widest = 0;
+    p.x_off[0] = ws;
+    ws += (size_t)rows * p.net.in0;
+    p.lds_bytes = p.head.lds_bytes;
+    for (int l = 0; l < n_layers; ++l) {
+        const CspLayerPlan& L = p.net.layer[l];
+        const CspHeadPlan f = p.fwd(l);
+        p.lds_bytes = std::max(p.lds_bytes, f.lds_bytes);
+        p.w_off[l] = off; off += f.packed_floats;
+        p.b_off[l] = off; off += L.n_pad();
+        if (L.layn) { p.g_off[l] = off; p.be_off[l] = off + L.n_pad(); off += 2 * (size_t)L.n_pad(); }
+        p.uw_off[l] = uoff; uoff += (size_t)L.out * L.in;
+        p.ub_off[l] = uoff; uoff += L.out;
+        if (L.layn) { p.ug_off[l] = uoff; p.ube_off[l] = uoff + L.out; uoff += 2 * (size_t)L.out; }
+        p.z_off[l] = ws; ws += (size_t)rows * L.out;
+        p.x_off[l + 1] = ws; ws += (size_t)rows * L.out;
+        p.widest = std::max(p.widest, std::max(L.in, L.out));
+    }
+    p.c_off = off; off += p.head.packed_floats;
+    p.uc_off = uoff; uoff += (size_t)C * p.net.out_width;
+    p.store_floats = off;
+    p.n_params = uoff;
+    for (int i = 0; i < 2; ++i) { p.dy_off[i] = ws; ws += (size_t)rows * p.widest; }
+    p.dz_off = ws; ws += (size_t)rows * p.widest;
+    p.dyx_off = ws; ws += (size_t)rows * p.widest;
+    if (ws * sizeof(float) + HEADFIT_MAX_WS > CSPFIT_MAX_WS) { p.why = "the saved activations of B + Bg rows exceed the 512 MiB workspace"; return p; }
+    p.g_ws_off = ws; ws += p.head.g_floats;
+    p.part_off = ws; ws += p.head.part_floats;
+    p.rowsum_off = ws; ws += p.head.rowsum_floats;
+    p.ws_floats = ws;
+    p.ws_bytes = ws * sizeof(float);
+    p.feat_grid = p.cap((rows * F + CSP_BLOCK - 1) / CSP_BLOCK);
+    p.row_grid = p.cap((rows + p.rows_per_wg - 1) / p.rows_per_wg);
+    p.valid = true;
+    return p;
+}
+
 }  // namespace range_host

@@ -15,6 +15,7 @@
 
 #include "../../include/range_hip.h"
 #include "../../include/range_headfit.h"
+#include "../../include/range_cspfit.h"
 #include "host_common.h"
 #include "host_copy.h"
 #include "host_plan.h"
@@ -35,6 +36,7 @@
 #include "csp_head_kernel.h"
 #include "csp_rank_kernel.h"
 #include "headfit_kernels.h"
+#include "cspfit_kernels.h"
 #include "checker_kernel.h"
 #include "neighbor_kernel.h"
 #include "kde_kernel.h"
@@ -53,6 +55,7 @@ using namespace range_host;
 #include "posenc_host.h"
 #include "csp_host.h"
 #include "headfit_host.h"
+#include "cspfit_host.h"
 #include "checker_host.h"
 #include "neighbor_host.h"
 #include "kde_host.h"

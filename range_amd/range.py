@@ -382,11 +382,38 @@ class CspLocationModel(nn.Module):
         self.num_classes = p.num_classes if p.class_emb is not None else 0
         self.spa_enc_type = p.spa_enc_type
         self._engine = [engine]
+        self._params = [p]
         engine.set_csp(p.kind, p.freq_list, p.widths, p.weights, p.biases, p.ln_gamma, p.ln_beta,
                        CSP_ACTIVATIONS[p.activation], p.skip_connection, p.use_layn)
         if p.class_emb is not None:
             engine.set_csp_head(p.class_emb)
         self.eval()
+
+    @property
+    def csp_params(self) -> CspParams:
+        """The ``CspParams`` of the installed network (the checkpoint's, or the last ``set_network``'s)."""
+        return self._params[0]
+
+    def set_network(self, p: CspParams) -> None:
+        """Install a whole network - a trained one (range_amd.csp_fit) - in place of the loaded one: the encoder
+        through the engine's ``set_csp`` and, when ``p.class_emb`` is set, its head through ``set_csp_head`` (without
+        one the model has no head afterwards: a head belongs to the network it was fitted behind).  The mirror
+        parameters, ``loc_emb_dim``, ``num_classes`` and ``spa_enc_type`` follow."""
+        tensors = list(p.weights) + list(p.biases) + [a for a in list(p.ln_gamma) + list(p.ln_beta) if a is not None]
+        if p.class_emb is not None:
+            tensors.append(p.class_emb)
+        if any(np.asarray(a).dtype != np.float32 or not np.isfinite(a).all() for a in tensors):
+            raise ValueError("set_network: every tensor must be float32 and finite")
+        eng = self._engine[0]
+        eng.set_csp(p.kind, p.freq_list, p.widths, p.weights, p.biases, p.ln_gamma, p.ln_beta,
+                    CSP_ACTIVATIONS[p.activation], p.skip_connection, p.use_layn)
+        if p.class_emb is not None:
+            eng.set_csp_head(p.class_emb)
+        self.loc_enc = _CspLocEnc(p, eng.device)
+        self.loc_emb_dim = p.num_filts
+        self.num_classes = p.num_classes if p.class_emb is not None else 0
+        self.spa_enc_type = p.spa_enc_type
+        self._params = [p]
 
     def set_class_head(self, weight) -> None:
         """Install a class head - a fitted one (range_amd.head_fit) - behind the network: ``weight`` (num_classes,

@@ -261,7 +261,7 @@ def make_csp_checkpoint(spa_enc_type: str = "gridcell", F: int = 32, hidden: int
                         act: str = "gelu", use_layn: bool = True, skip: bool = True, num_filts: int = 256,
                         min_radius: float = 0.001, max_radius: float = 360.0, seed: int = 77,
                         freq_init: str = "geometric", num_classes: int = 5, cnn_feat_dim: int = 8,
-                        device: str = "cuda:3", class_scale: float = 1.0) -> Dict[str, object]:
+                        device: str = "cuda:3", class_scale: float = 1.0, dropout: float = 0.5) -> Dict[str, object]:
     """A checkpoint dict with the reference's key names: ``params`` as ``get_csp`` / ``get_model`` /
     ``get_ffn`` read them and the ``state_dict`` of a ``LocationImageEncoder`` - the feed-forward net under
     ``loc_enc.spa_enc.ffn.layers.{i}.linear.*`` / ``.layernorm.*`` (float32, numpy-seeded: Xavier-uniform
@@ -270,7 +270,8 @@ def make_csp_checkpoint(spa_enc_type: str = "gridcell", F: int = 32, hidden: int
     each under its aliases).  ``layers``: num_hidden_layer (0: one layer from the features to num_filts).
     ``device``: ``params['device']``, the training job's - the reference moves the model there (load_csp.py:21),
     range_amd ignores it.  ``class_scale``: ``class_emb`` is N(0, 1) times this, applied after every draw (no
-    other tensor changes with it) - small enough, the class head's sigmoid does not saturate."""
+    other tensor changes with it) - small enough, the class head's sigmoid does not saturate.  ``dropout``:
+    ``params['dropout']`` (no tensor depends on it)."""
     import torch
 
     rng = np.random.default_rng(seed)
@@ -305,7 +306,7 @@ def make_csp_checkpoint(spa_enc_type: str = "gridcell", F: int = 32, hidden: int
         "cnn_feat_dim": cnn_feat_dim, "map_range": (-180, 180, -90, 90), "frequency_num": F,
         "max_radius": max_radius, "min_radius": min_radius, "spa_f_act": act, "freq_init": freq_init,
         "num_rbf_anchor_pts": 200, "rbf_kernal_size": 1.0, "spa_enc_use_postmat": True,
-        "num_hidden_layer": layers, "dropout": 0.5, "hidden_dim": hidden, "use_layn": use_layn,
+        "num_hidden_layer": layers, "dropout": dropout, "hidden_dim": hidden, "use_layn": use_layn,
         "skip_connection": skip, "dataset": "fmow", "lr": 0.001,
     }
     return {"params": params, "state_dict": sd}
