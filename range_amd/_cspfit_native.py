@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _native
+from ._headfit_native import step_rows
 from ._native import HipEngine, RangeNativeError, _check, _ptr  # noqa: F401
 from .csp import ACTIVATIONS, CspParams
 
@@ -144,30 +145,7 @@ class CspFit:
 
     def _rows(self, lonlat: torch.Tensor, rows: Optional[torch.Tensor], labels: torch.Tensor, bg: Optional[torch.Tensor],
               weight: float, validate: bool):
-        e, C_ = self.engine, self.num_classes
-        if not C_:
-            raise RangeNativeError("no CSP fit begun on this engine (begin)")
-        e._t(lonlat, torch.float64, (2,))
-        e._t(labels, torch.int32, ())
-        N, B = lonlat.shape[0], labels.shape[0]
-        if rows is not None:
-            e._t(rows, torch.int32, ())
-            if rows.shape[0] != B:
-                raise ValueError(f"{rows.shape[0]} row ids for {B} labels")
-        elif N < B:
-            raise ValueError(f"{B} labels without row ids: there are {N} locations")
-        Bg = 0
-        if bg is not None:
-            e._t(bg, torch.float64, (2,))
-            Bg = bg.shape[0]
-        if B < 1 or B + Bg > MAX_ROWS:
-            raise ValueError(f"B = {B}, Bg = {Bg}: 1 <= B and B + Bg <= {MAX_ROWS}")
-        if validate:
-            if bool(((labels < 0) | (labels >= C_)).any()):
-                raise ValueError(f"a label outside 0 .. {C_ - 1}")
-            if rows is not None and bool(((rows < 0) | (rows >= N)).any()):
-                raise ValueError(f"a row id outside 0 .. {N - 1}")
-        return [self._h, lonlat.data_ptr(), N, _ptr(rows), labels.data_ptr(), B, _ptr(bg if Bg else None), Bg, float(weight)]
+        return step_rows(self, "CSP", "there are {} locations", torch.float64, (2,), lonlat, rows, labels, bg, weight, validate)
 
     def step(self, lonlat: torch.Tensor, rows: Optional[torch.Tensor], labels: torch.Tensor, bg: Optional[torch.Tensor],
              lr: float, weight: float = 1.0, weight_decay: float = 0.0, beta1: float = 0.9, beta2: float = 0.999,

@@ -66,6 +66,38 @@ def plan(num_classes: int, width: int, rows: int, max_grid: int = 0, panel_cols:
     return dict(zip(keys, (int(v) for v in out)))
 
 
+def step_rows(fit, noun: str, have: str, dtype: torch.dtype, trail: tuple, data: torch.Tensor, rows: Optional[torch.Tensor],
+              labels: torch.Tensor, bg: Optional[torch.Tensor], weight: float, validate: bool) -> list:
+    """The checks of a step's rows and the leading arguments of its call, for ``HeadFit`` and ``_cspfit_native.CspFit``:
+    ``data`` and ``bg`` are ``dtype`` tensors (n,) + ``trail``; ``noun`` names the fit and ``have`` what ``data`` has
+    in the messages."""
+    e, C_ = fit.engine, fit.num_classes
+    if not C_:
+        raise RangeNativeError(f"no {noun} fit begun on this engine (begin)")
+    e._t(data, dtype, trail)
+    e._t(labels, torch.int32, ())
+    N, B = data.shape[0], labels.shape[0]
+    if rows is not None:
+        e._t(rows, torch.int32, ())
+        if rows.shape[0] != B:
+            raise ValueError(f"{rows.shape[0]} row ids for {B} labels")
+    elif N < B:
+        raise ValueError(f"{B} labels without row ids: " + have.format(N))
+    Bg = 0
+    if bg is not None:
+        e._t(bg, dtype, trail)
+        Bg = bg.shape[0]
+    if B < 1 or B + Bg > MAX_ROWS:
+        raise ValueError(f"B = {B}, Bg = {Bg}: 1 <= B and B + Bg <= {MAX_ROWS}")
+    if validate:
+        # (device reads: a synchronisation; the fitting loops validate their host arrays once instead)
+        if bool(((labels < 0) | (labels >= C_)).any()):
+            raise ValueError(f"a label outside 0 .. {C_ - 1}")
+        if rows is not None and bool(((rows < 0) | (rows >= N)).any()):
+            raise ValueError(f"a row id outside 0 .. {N - 1}")
+    return [fit._h, data.data_ptr(), N, _ptr(rows), labels.data_ptr(), B, _ptr(bg if Bg else None), Bg, float(weight)]
+
+
 class HeadFit:
     """The class-head fit of one engine context."""
 
@@ -102,31 +134,8 @@ class HeadFit:
 
     def _rows(self, feats: torch.Tensor, rows: Optional[torch.Tensor], labels: torch.Tensor, bg: Optional[torch.Tensor],
               weight: float, validate: bool):
-        e, F_, C_ = self.engine, self.width, self.num_classes
-        if not C_:
-            raise RangeNativeError("no class-head fit begun on this engine (begin)")
-        e._t(feats, torch.float32, (F_,))
-        e._t(labels, torch.int32, ())
-        N, B = feats.shape[0], labels.shape[0]
-        if rows is not None:
-            e._t(rows, torch.int32, ())
-            if rows.shape[0] != B:
-                raise ValueError(f"{rows.shape[0]} row ids for {B} labels")
-        elif N < B:
-            raise ValueError(f"{B} labels without row ids: the feature matrix has {N} rows")
-        Bg = 0
-        if bg is not None:
-            e._t(bg, torch.float32, (F_,))
-            Bg = bg.shape[0]
-        if B < 1 or B + Bg > MAX_ROWS:
-            raise ValueError(f"B = {B}, Bg = {Bg}: 1 <= B and B + Bg <= {MAX_ROWS}")
-        if validate:
-            # (device reads: a synchronisation; the fitting loops validate their host arrays once instead)
-            if bool(((labels < 0) | (labels >= C_)).any()):
-                raise ValueError(f"a label outside 0 .. {C_ - 1}")
-            if rows is not None and bool(((rows < 0) | (rows >= N)).any()):
-                raise ValueError(f"a row id outside 0 .. {N - 1}")
-        return [self._h, feats.data_ptr(), N, _ptr(rows), labels.data_ptr(), B, _ptr(bg if Bg else None), Bg, float(weight)]
+        return step_rows(self, "class-head", "the feature matrix has {} rows", torch.float32, (self.width,), feats, rows, labels, bg,
+                         weight, validate)
 
     def step(self, feats: torch.Tensor, rows: Optional[torch.Tensor], labels: torch.Tensor, bg: Optional[torch.Tensor],
              lr: float, weight: float = 1.0, weight_decay: float = 0.0, beta1: float = 0.9, beta2: float = 0.999,

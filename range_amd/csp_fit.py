@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from .csp import CspParams
-from .head_fit import NEG_RAND_TYPES, _labels, balanced_indices, rand_locations
+from .head_fit import NEG_RAND_TYPES, _labels, _locs64, _run_epochs, rand_locations
 
 
 @dataclass
@@ -55,15 +55,6 @@ def xavier_params(p: CspParams, num_classes: int, seed: int) -> CspParams:
     a = 1.0 / math.sqrt(p.num_filts)
     head = rng.uniform(-a, a, size=(num_classes, p.num_filts)).astype(np.float32)
     return dataclasses.replace(p, weights=ws, biases=bs, ln_gamma=gs, ln_beta=bes, num_classes=num_classes, class_emb=head)
-
-
-def _locs64(locs, what: str) -> np.ndarray:
-    a = locs.detach().cpu().numpy() if torch.is_tensor(locs) else np.asarray(locs)
-    if a.ndim != 2 or a.shape[1] != 2:
-        raise ValueError(f"{what}: (n, 2) lon / lat degrees, got {a.shape}")
-    if not np.isfinite(a).all():
-        raise ValueError(f"{what}: non-finite entries")
-    return np.ascontiguousarray(a, dtype=np.float64)
 
 
 def fit_location_model(model, train_locs, train_classes, num_classes: Optional[int] = None, *, epochs: int = 30,
@@ -117,34 +108,15 @@ def fit_location_model(model, train_locs, train_classes, num_classes: Optional[i
         val_locs = torch.from_numpy(_locs64(val[0], "val locations")).to(dev)
         vl, _ = _labels(val[1], val_locs.shape[0], C)
         val_lab = torch.from_numpy(vl.astype(np.int32)).to(dev)
-    train_losses, val_losses = [], ([] if val is not None else None)
-    for epoch in range(epochs):
-        if batches is not None:
-            plan = [(np.asarray(r, dtype=np.int64), spec) for r, spec in batches[epoch]]
-        else:
-            idx = balanced_indices(lab, max_num_exs_per_class, rng) if balanced else rng.permutation(N)
-            plan = [(idx[i:i + batch_size], None) for i in range(0, len(idx), batch_size)]
-        losses, sizes = [], []
-        for rows, spec in plan:
-            if rows.ndim != 1 or not 1 <= len(rows) <= MAX_ROWS or rows.min() < 0 or rows.max() >= N:
-                raise ValueError(f"a batch's row ids: 1 .. {MAX_ROWS} integers in 0 .. {N - 1}")
-            rows_dev = torch.from_numpy(rows.astype(np.int32)).to(dev)
-            bg = spec if spec is not None else rand_locations(rng.random((len(rows), 3), dtype=np.float32), neg_rand_type)
-            bg_dev = torch.from_numpy(_locs64(bg, "background locations")).to(dev) if len(bg) else None
-            losses.append(fit.step(locs_dev, rows_dev, lab_dev[rows_dev.long()], bg_dev, lr * lr_decay ** epoch,
-                                   weight=rand_sample_weight, weight_decay=weight_decay, dropout=drop, seed=seed))
-            sizes.append(len(rows))
-        per_step = torch.stack(losses)[:, 0].double().cpu().numpy()
-        train_losses.append(float(np.average(per_step, weights=np.asarray(sizes, dtype=np.float64))))
-        if val is not None:
-            vs, vn = [], []
-            for i in range(0, val_locs.shape[0], batch_size):
-                j = min(val_locs.shape[0], i + batch_size)
-                vs.append(fit.loss(val_locs[i:j], None, val_lab[i:j], None))      # (eval mode: no dropout)
-                vn.append(j - i)
-            v = torch.stack(vs)[:, 2].double().cpu().numpy()
-            val_losses.append(float(np.average(v, weights=np.asarray(vn, dtype=np.float64))))
-        if logger is not None:
-            logger.info("Epoch {}\tLoss  : {:.4f}".format(epoch, train_losses[-1]) +
-                        ("\tTest loss   : {:.4f}".format(val_losses[-1]) if val is not None else ""))
+
+    def step(rows_dev, spec, lr_epoch):
+        bg = spec if spec is not None else rand_locations(rng.random((len(rows_dev), 3), dtype=np.float32), neg_rand_type)
+        bg_dev = torch.from_numpy(_locs64(bg, "background locations")).to(dev) if len(bg) else None
+        return fit.step(locs_dev, rows_dev, lab_dev[rows_dev.long()], bg_dev, lr_epoch, weight=rand_sample_weight,
+                        weight_decay=weight_decay, dropout=drop, seed=seed)
+
+    train_losses, val_losses = _run_epochs(          # (validation in eval mode: no dropout)
+        step, None if val is None else lambda i, j: fit.loss(val_locs[i:j], None, val_lab[i:j], None),
+        0 if val is None else val_locs.shape[0], N, lab, dev, epochs=epochs, batch_size=batch_size, batches=batches, balanced=balanced,
+        max_num_exs_per_class=max_num_exs_per_class, lr=lr, lr_decay=lr_decay, rng=rng, logger=logger)
     return CspFitResult(fit.trained(), train_losses, val_losses, fit.steps)

@@ -18,6 +18,29 @@ static void (*csp_head_kernel_for(int m_tiles, int mode))(CspHeadArgs) {
     return csp_head_kernels[m_tiles - 1][mode];
 }
 
+// One launch of it by plan `p`, in the plan's mode: the B rows of x against the packed w, columns `ids` or all, into
+// out.  Shared with the layers' forward products of the CSP encoder fit (cspfit_host.h).
+static int csp_head_launch(const CspHeadPlan& p, const float* x, const float* w, const int32_t* ids, float* out, int64_t B,
+                           hipStream_t s) {
+    CspHeadArgs a{};
+    a.x = x;
+    a.w4 = reinterpret_cast<const float4*>(w);
+    a.ids = ids;
+    a.out = out;
+    a.B = B;
+    a.n_items = p.n_items;
+    a.K = p.num_filts;
+    a.k_groups = p.k_groups;
+    a.ld = p.ld;
+    a.M = p.M;
+    a.col_tiles = p.col_tiles;
+    a.n_chunks = p.n_chunks;
+    a.num_classes = p.num_classes;
+    a.chunks_per_item = p.chunks_per_item;
+    a.groups = p.groups;
+    return launch(csp_head_kernel_for(p.m_tiles, p.mode), dim3(p.grid), dim3(p.block), p.lds_bytes, s, a);
+}
+
 // ---- the evaluation behind the head (csp_rank_kernel.h), by tile height, image predictions and embeddings
 static void (*csp_rank_kernel_for(int m_tiles, int img_kind, bool has_head))(CspRankArgs) {
     static void (*const with_head[2][CSP_IMG_KINDS])(CspRankArgs) = {
@@ -189,23 +212,7 @@ int range_csp_head_grid(range_ctx* c, const float* feats, int64_t B, const int32
     const CspHeadPlan p = csp_head_plan(m.plan.out_width, m.num_classes, M, B, mode, max_grid);
     if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %lld, M = %d: %s", (long long)B, M, p.why);
     ENTER_DEVICE(c);
-    CspHeadArgs a{};
-    a.x = feats;
-    a.w4 = reinterpret_cast<const float4*>(m.d_head.p);
-    a.ids = ids;
-    a.out = out;
-    a.B = B;
-    a.n_items = p.n_items;
-    a.K = p.num_filts;
-    a.k_groups = p.k_groups;
-    a.ld = p.ld;
-    a.M = p.M;
-    a.col_tiles = p.col_tiles;
-    a.n_chunks = p.n_chunks;
-    a.num_classes = p.num_classes;
-    a.chunks_per_item = p.chunks_per_item;
-    a.groups = p.groups;
-    return launch(csp_head_kernel_for(p.m_tiles, mode), dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, a);
+    return csp_head_launch(p, feats, m.d_head.p, ids, out, B, (hipStream_t)stream);
 }
 
 int range_csp_head(range_ctx* c, const float* feats, int64_t B, const int32_t* ids, int32_t M, int32_t mode, float* out,

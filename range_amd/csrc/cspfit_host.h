@@ -1,8 +1,7 @@
 // Host side of the CSP encoder fit (cspfit_kernels.h; include/range_cspfit.h).  Part of range_hip.hip's translation
-// unit, behind engine_ctx.h, csp_host.h and headfit_host.h (whose kernel tables and Adam scalars it uses).
+// unit, behind engine_ctx.h, csp_host.h (the class head's launch) and headfit_host.h (the row checks, the head pass, the
+// update launch, Adam's scalars and HEADFIT_STEP / _GRAD / _LOSS, which name what a call does here too).
 #pragma once
-
-enum { CSPFIT_STEP = 0, CSPFIT_GRAD = 1, CSPFIT_LOSS = 2 };
 
 static void (*cspfit_fwd_row_for(int act))(CspfitRowArgs) {
     static void (*const k[CSP_ACTS])(CspfitRowArgs) = {cspfit_fwd_row_kernel<0>, cspfit_fwd_row_kernel<1>, cspfit_fwd_row_kernel<2>,
@@ -13,11 +12,6 @@ static void (*cspfit_bwd_row_for(int act))(CspfitRowArgs) {
     static void (*const k[CSP_ACTS])(CspfitRowArgs) = {cspfit_bwd_row_kernel<0>, cspfit_bwd_row_kernel<1>, cspfit_bwd_row_kernel<2>,
                                                       cspfit_bwd_row_kernel<3>, cspfit_bwd_row_kernel<4>};
     return k[act];
-}
-
-static uint32_t cspfit_mix_host(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
 }
 
 static CspfitPlan cspfit_plan_of(const range_ctx::Cspfit& f, int64_t R, int64_t max_grid, int32_t panel_cols) {
@@ -33,13 +27,9 @@ static int cspfit_run(range_ctx* c, int what, const double* lonlat, int64_t N, c
     if (!c || !lonlat || !labels) return fail(RANGE_ERR_INVALID, "null argument");
     range_ctx::Cspfit& f = c->cf;
     if (!f.C) return fail(RANGE_ERR_STATE, "no CSP fit begun (range_cspfit_begin)");
-    if (what == CSPFIT_GRAD && !grads) return fail(RANGE_ERR_INVALID, "null argument");
-    if (what == CSPFIT_LOSS && !loss3 && !emb) return fail(RANGE_ERR_INVALID, "null argument");
-    if (N < 1 || B < 1 || Bg < 0) return fail(RANGE_ERR_INVALID, "N and B must be > 0, Bg >= 0");
-    if ((bg != nullptr) != (Bg > 0)) return fail(RANGE_ERR_INVALID, "Bg = %d %s background locations", Bg, bg ? "with" : "without");
-    if (!rows && N < B) return fail(RANGE_ERR_INVALID, "B = %d rows without row ids: there are %lld locations", B, (long long)N);
-    if (N > (INT64_C(1) << 40)) return fail(RANGE_ERR_INVALID, "N beyond 2^40");
-    if (!std::isfinite(weight)) return fail(RANGE_ERR_INVALID, "rand_sample_weight must be finite");
+    if (what == HEADFIT_GRAD && !grads) return fail(RANGE_ERR_INVALID, "null argument");
+    if (what == HEADFIT_LOSS && !loss3 && !emb) return fail(RANGE_ERR_INVALID, "null argument");
+    if (int rc = headfit_check_rows(N, rows, B, bg, Bg, weight, true)) return rc;
     if (!(drop_p >= 0.0 && drop_p < 1.0)) return fail(RANGE_ERR_INVALID, "dropout_p must be in [0, 1)");
     if (!aligned(lonlat, 8) || !aligned(bg, 8) || !aligned(rows, 4) || !aligned(labels, 4) || !aligned(grads, 4) || !aligned(loss3, 4) ||
         !aligned(emb, 4))
@@ -48,7 +38,8 @@ static int cspfit_run(range_ctx* c, int what, const double* lonlat, int64_t N, c
     const CspfitPlan p = cspfit_plan_of(f, R, max_grid, panel_cols);
     if (!p.valid) return fail(RANGE_ERR_INVALID, "B = %d, Bg = %d: %s", B, Bg, p.why);
     HeadfitUpdateArgs u{};
-    if (what == CSPFIT_STEP)
+    const bool step = what == HEADFIT_STEP;
+    if (step)
         if (int rc = headfit_adam_scalars(*adam, f.steps, u)) return rc;
     ENTER_DEVICE(c);
     if (f.ws.ensure(p.ws_floats) != hipSuccess) return fail(RANGE_ERR_NOMEM, "out of device memory (%zu bytes of workspace)", p.ws_bytes);
@@ -61,7 +52,7 @@ static int cspfit_run(range_ctx* c, int what, const double* lonlat, int64_t N, c
     const bool drop_on = drop_p > 0.0;
     const uint32_t thresh = (uint32_t)std::floor((1.0 - drop_p) * 16777216.0);
     const float drop_scale = (float)(1.0 / (1.0 - drop_p));
-    const uint32_t key0 = cspfit_mix_host(cspfit_mix_host(cspfit_mix_host((uint32_t)drop_seed) ^ (uint32_t)(drop_seed >> 32)) ^ (uint32_t)f.steps);
+    const uint32_t key0 = cspfit_mix(cspfit_mix(cspfit_mix((uint32_t)drop_seed) ^ (uint32_t)(drop_seed >> 32)) ^ (uint32_t)f.steps);
     auto row_args = [&](int l) {
         const CspLayerPlan& lp = p.net.layer[l];
         CspfitRowArgs r{};
@@ -74,7 +65,7 @@ static int cspfit_run(range_ctx* c, int what, const double* lonlat, int64_t N, c
         r.n = lp.out;
         r.lpr = p.lpr;
         r.drop_on = drop_on;
-        r.drop_key = cspfit_mix_host(key0 ^ (uint32_t)l);
+        r.drop_key = cspfit_mix(key0 ^ (uint32_t)l);
         r.drop_thresh = thresh;
         r.drop_scale = drop_scale;
         return r;
@@ -84,103 +75,40 @@ static int cspfit_run(range_ctx* c, int what, const double* lonlat, int64_t N, c
                         (int32_t)R, (int32_t)f.F, (int32_t)f.kind, (int32_t)p.net.in0, ws + p.x_off[0]))
         return rc;
     for (int l = 0; l < L; ++l) {
-        const CspHeadPlan h = p.fwd(l);
-        CspHeadArgs a{};
-        a.x = ws + p.x_off[l];
-        a.w4 = reinterpret_cast<const float4*>(prm + p.w_off[l]);
-        a.out = ws + p.z_off[l];
-        a.B = R;
-        a.n_items = h.n_items;
-        a.K = h.num_filts;
-        a.k_groups = h.k_groups;
-        a.ld = h.ld;
-        a.M = h.M;
-        a.col_tiles = h.col_tiles;
-        a.n_chunks = h.n_chunks;
-        a.num_classes = h.num_classes;
-        a.chunks_per_item = h.chunks_per_item;
-        a.groups = h.groups;
-        if (int rc = launch(csp_head_kernel_for(h.m_tiles, CSP_HEAD_LOGITS), dim3(h.grid), dim3(h.block), h.lds_bytes, s, a)) return rc;
+        if (int rc = csp_head_launch(p.fwd(l), ws + p.x_off[l], prm + p.w_off[l], nullptr, ws + p.z_off[l], R, s)) return rc;
         CspfitRowArgs r = row_args(l);
         r.y = ws + p.x_off[l + 1];
         if (int rc = launch(cspfit_fwd_row_for(f.act), dim3(p.row_grid), dim3(p.block), 0, s, r)) return rc;
     }
     float* const E = ws + p.x_off[L];
     if (emb) HIP_TRY(hipMemcpyAsync(emb, E, (size_t)R * nf * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (what == CSPFIT_LOSS && !loss3) return RANGE_OK;
-    // ---- the head, panel by panel
+    if (what == HEADFIT_LOSS && !loss3) return RANGE_OK;
+    // ---- the head (headfit_host.h), with dE = G W_c behind every panel's gradient, before the panel's update: the
+    // product reads the panel's columns of W_c as the step found them
     const HeadfitPlan& hp = p.head;
+    float* const wc = prm + p.c_off;
     float* const g = ws + p.g_ws_off;
-    float* const parts = ws + p.part_off;
-    float* const rowsum = ws + p.rowsum_off;
     float* dy[2] = {ws + p.dy_off[0], ws + p.dy_off[1]};
-    const double bc = (double)B * f.C;
-    for (int pn = 0; pn < hp.n_panels; ++pn) {
-        HeadfitGradArgs a{};
-        a.x = E;
-        a.w4 = reinterpret_cast<const float4*>(prm + p.c_off);
-        a.labels = labels;
-        a.g = g;
-        a.parts = parts;
-        a.n_items = hp.grad_items(pn);
-        a.R = (int32_t)R;
-        a.B = B;
-        a.K = nf;
-        a.k_groups = hp.k_groups;
-        a.ld = hp.ld;
-        a.C = f.C;
-        a.tile0 = hp.panel_first_tile(pn);
-        a.n_tiles = hp.panel_n_tiles(pn);
-        a.n_chunks = hp.grad_chunks(pn);
-        a.panel_tiles = hp.panel_tiles;
-        a.panel_cols = hp.panel_cols;
-        a.s_neg = (float)(1.0 / bc);
-        a.s_lab = (float)(-(double)f.C / bc);
-        a.s_bg = Bg ? (float)(weight / ((double)Bg * f.C)) : 0.0f;
-        if (int rc = launch(headfit_grad_kernel_for(hp.m_tiles, what != CSPFIT_LOSS), dim3(hp.grad_grid(pn)), dim3(hp.block), hp.lds_bytes, s, a))
-            return rc;
-        if (loss3)
-            if (int rc = launch(headfit_fold_kernel, dim3(hp.row_grid), dim3(hp.block), 0, s, (const float*)parts, rowsum, (int32_t)R,
-                                a.n_tiles, a.panel_tiles, (int32_t)(pn == 0)))
-                return rc;
-        if (what == CSPFIT_LOSS) continue;
+    auto back_head = [&](int pn, int tile0, int n_tiles) {
         CspfitBackArgs b{};
         b.a = g;
-        b.w = prm + p.c_off;
+        b.w = wc;
         b.out = dy[0];
         b.n_items = p.back_items(nf);
         b.R = (int32_t)R;
         b.lda = hp.panel_cols;
-        b.c0 = a.tile0 * 32;
-        b.kc = std::min(a.n_tiles * 32, f.C - b.c0);
+        b.c0 = tile0 * 32;
+        b.kc = std::min(n_tiles * 32, f.C - b.c0);
         b.k_groups = hp.k_groups;
         b.N = nf;
         b.col_groups = p.back_col_groups(nf);
         b.first = pn == 0;
-        if (int rc = launch(cspfit_back_kernel, dim3(p.back_grid(nf)), dim3(p.block), 0, s, b)) return rc;
-        u.x = E;
-        u.g = g;
-        u.w = prm + p.c_off;
-        u.m = u.w + m_delta;
-        u.v = u.w + v_delta;
-        u.dw = what == CSPFIT_GRAD ? grads + p.uc_off : nullptr;
-        u.n_items = hp.update_items(pn);
-        u.R = (int32_t)R;
-        u.K = nf;
-        u.k_groups = hp.k_groups;
-        u.C = f.C;
-        u.tile0 = a.tile0;
-        u.panel_cols = hp.panel_cols;
-        u.f_groups = hp.f_groups;
-        if (int rc = launch(what == CSPFIT_STEP ? headfit_update_kernel<true> : headfit_update_kernel<false>, dim3(hp.update_grid(pn)),
-                            dim3(hp.block), 0, s, u))
-            return rc;
-    }
-    if (loss3)
-        if (int rc = launch(headfit_loss_kernel, dim3(1), dim3(hp.block), 0, s, (const float*)rowsum, (int32_t)R, B, (int32_t)f.C, (float)weight,
-                            loss3))
-            return rc;
-    if (what == CSPFIT_LOSS) return RANGE_OK;
+        return launch(cspfit_back_kernel, dim3(p.back_grid(nf)), dim3(p.block), 0, s, b);
+    };
+    if (int rc = headfit_head_pass(what, hp, E, wc, wc + m_delta, wc + v_delta, g, ws + p.part_off, ws + p.rowsum_off, labels, B, Bg, weight,
+                                   u, what == HEADFIT_GRAD ? grads + p.uc_off : nullptr, loss3, nullptr, s, back_head))
+        return rc;
+    if (what == HEADFIT_LOSS) return RANGE_OK;
     // ---- the layers backward; dy[cur] holds the gradient of layer l's output
     int cur = 0;
     for (int l = L - 1; l >= 0; --l) {
@@ -196,11 +124,11 @@ static int cspfit_run(range_ctx* c, int what, const double* lonlat, int64_t N, c
         CspfitColsumArgs cs{};
         cs.src0 = dz; cs.src1 = dyx; cs.src2 = dy[cur];
         cs.p0 = prm + p.b_off[l]; cs.p1 = prm + p.g_off[l]; cs.p2 = prm + p.be_off[l];
-        if (what == CSPFIT_GRAD) { cs.out0 = grads + p.ub_off[l]; cs.out1 = grads + p.ug_off[l]; cs.out2 = grads + p.ube_off[l]; }
+        if (what == HEADFIT_GRAD) { cs.out0 = grads + p.ub_off[l]; cs.out1 = grads + p.ug_off[l]; cs.out2 = grads + p.ube_off[l]; }
         cs.m_delta = m_delta; cs.v_delta = v_delta;
         cs.R = (int32_t)R; cs.n = lp.out; cs.kinds = p.colsum_kinds(l);
         cs.adam = u;
-        if (int rc = launch(what == CSPFIT_STEP ? cspfit_colsum_kernel<true> : cspfit_colsum_kernel<false>, dim3(p.colsum_grid(l)),
+        if (int rc = launch(step ? cspfit_colsum_kernel<true> : cspfit_colsum_kernel<false>, dim3(p.colsum_grid(l)),
                             dim3(CSPFIT_COLSUM_BLOCK), 0, s, cs))
             return rc;
         const HeadfitPlan up = p.upd(l);
@@ -221,26 +149,13 @@ static int cspfit_run(range_ctx* c, int what, const double* lonlat, int64_t N, c
             b.first = 1;
             if (int rc = launch(cspfit_back_kernel, dim3(p.back_grid(lp.in)), dim3(p.block), 0, s, b)) return rc;
         }
-        u.x = ws + p.x_off[l];
-        u.g = dz;
-        u.w = prm + p.w_off[l];
-        u.m = u.w + m_delta;
-        u.v = u.w + v_delta;
-        u.dw = what == CSPFIT_GRAD ? grads + p.uw_off[l] : nullptr;
-        u.n_items = up.update_items(0);
-        u.R = (int32_t)R;
-        u.K = lp.in;
-        u.k_groups = up.k_groups;
-        u.C = lp.out;
-        u.tile0 = 0;
-        u.panel_cols = lp.out;           // (the row stride of dZ)
-        u.f_groups = up.f_groups;
-        if (int rc = launch(what == CSPFIT_STEP ? headfit_update_kernel<true> : headfit_update_kernel<false>, dim3(up.update_grid(0)),
-                            dim3(up.block), 0, s, u))
+        float* const w = prm + p.w_off[l];
+        if (int rc = headfit_update_launch(step, u, ws + p.x_off[l], dz, w, w + m_delta, w + v_delta,
+                                           what == HEADFIT_GRAD ? grads + p.uw_off[l] : nullptr, up, 0, lp.out, s))   // (dZ's row stride)
             return rc;
         cur = 1 - cur;
     }
-    if (what == CSPFIT_STEP) ++f.steps;
+    if (step) ++f.steps;
     return RANGE_OK;
 }
 
@@ -318,7 +233,7 @@ int range_cspfit_step_grid(range_ctx* c, const double* lonlat, int64_t N, const 
                            double weight_decay, double dropout_p, uint64_t dropout_seed, float* loss3, int64_t max_grid,
                            int32_t panel_cols, range_stream_t stream) {
     const HeadfitAdam adam{lr, beta1, beta2, eps, weight_decay};
-    return cspfit_run(c, CSPFIT_STEP, lonlat, N, rows, labels, B, bg, Bg, rand_sample_weight, &adam, dropout_p, dropout_seed, nullptr,
+    return cspfit_run(c, HEADFIT_STEP, lonlat, N, rows, labels, B, bg, Bg, rand_sample_weight, &adam, dropout_p, dropout_seed, nullptr,
                       loss3, nullptr, max_grid, panel_cols, stream);
 }
 
@@ -332,7 +247,7 @@ int range_cspfit_step(range_ctx* c, const double* lonlat, int64_t N, const int32
 int range_cspfit_grad_grid(range_ctx* c, const double* lonlat, int64_t N, const int32_t* rows, const int32_t* labels, int32_t B,
                            const double* bg, int32_t Bg, double rand_sample_weight, double dropout_p, uint64_t dropout_seed,
                            float* grads, float* loss3, int64_t max_grid, int32_t panel_cols, range_stream_t stream) {
-    return cspfit_run(c, CSPFIT_GRAD, lonlat, N, rows, labels, B, bg, Bg, rand_sample_weight, nullptr, dropout_p, dropout_seed, grads,
+    return cspfit_run(c, HEADFIT_GRAD, lonlat, N, rows, labels, B, bg, Bg, rand_sample_weight, nullptr, dropout_p, dropout_seed, grads,
                       loss3, nullptr, max_grid, panel_cols, stream);
 }
 
@@ -346,7 +261,7 @@ int range_cspfit_grad(range_ctx* c, const double* lonlat, int64_t N, const int32
 int range_cspfit_loss(range_ctx* c, const double* lonlat, int64_t N, const int32_t* rows, const int32_t* labels, int32_t B,
                       const double* bg, int32_t Bg, double rand_sample_weight, double dropout_p, uint64_t dropout_seed, float* loss3,
                       float* emb, range_stream_t stream) {
-    return cspfit_run(c, CSPFIT_LOSS, lonlat, N, rows, labels, B, bg, Bg, rand_sample_weight, nullptr, dropout_p, dropout_seed, nullptr,
+    return cspfit_run(c, HEADFIT_LOSS, lonlat, N, rows, labels, B, bg, Bg, rand_sample_weight, nullptr, dropout_p, dropout_seed, nullptr,
                       loss3, emb, 0, 0, stream);
 }
 

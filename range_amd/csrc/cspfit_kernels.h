@@ -36,7 +36,8 @@
 
 namespace range_hip {
 
-__device__ __forceinline__ uint32_t cspfit_mix(uint32_t x) {
+// (also on the host: cspfit_host.h derives the per-layer dropout keys with it)
+__host__ __device__ __forceinline__ uint32_t cspfit_mix(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
 }

@@ -1,8 +1,8 @@
 // Host side of the class-head fit (headfit_kernels.h; include/range_headfit.h).  Part of range_hip.hip's translation
-// unit, behind engine_ctx.h.
+// unit, behind engine_ctx.h.  The CSP encoder fit (cspfit_host.h) runs the same row checks, head pass and update launch.
 #pragma once
 
-enum { HEADFIT_STEP = 0, HEADFIT_GRAD = 1, HEADFIT_LOSS = 2 };
+enum { HEADFIT_STEP = 0, HEADFIT_GRAD = 1, HEADFIT_LOSS = 2 };   // what a call of either fit does
 
 struct HeadfitAdam { double lr, beta1, beta2, eps, weight_decay; };
 
@@ -30,8 +30,89 @@ static void (*headfit_grad_kernel_for(int m_tiles, bool write_g))(HeadfitGradArg
     return kernels[m_tiles - 1][write_g];
 }
 
-// One call on the step's rows: the gather, then per class panel the logit gradient, the fold of its row sums and
-// (HEADFIT_STEP: Adam; HEADFIT_GRAD: dW stored) the update, then the loss scalars.
+// The checks of a step's rows that both fits make; `locations`: the rows are the CSP fit's locations, not features.
+static int headfit_check_rows(int64_t N, const int32_t* rows, int32_t B, const void* bg, int32_t Bg, double weight, bool locations) {
+    if (N < 1 || B < 1 || Bg < 0) return fail(RANGE_ERR_INVALID, "N and B must be > 0, Bg >= 0");
+    if ((bg != nullptr) != (Bg > 0))
+        return fail(RANGE_ERR_INVALID, "Bg = %d %s background %s", Bg, bg ? "with" : "without", locations ? "locations" : "rows");
+    if (!rows && N < B)
+        return fail(RANGE_ERR_INVALID, locations ? "B = %d rows without row ids: there are %lld locations"
+                                                 : "B = %d rows without row ids: the feature matrix has %lld", B, (long long)N);
+    if (N > (INT64_C(1) << 40)) return fail(RANGE_ERR_INVALID, "N beyond 2^40");
+    if (!std::isfinite(weight)) return fail(RANGE_ERR_INVALID, "rand_sample_weight must be finite");
+    return RANGE_OK;
+}
+
+// One launch of headfit_update_kernel for panel `pn` of plan `p` (its rows, K = p.F, C = p.C): dW = G^T X of the
+// panel's classes from x and g (row stride `ldg`), into Adam on (w, m, v) with `u`'s scalars or (`adam` false) into
+// dw.  Shared with the layers' dW of the CSP encoder fit.
+static int headfit_update_launch(bool adam, HeadfitUpdateArgs u, const float* x, const float* g, float* w, float* m, float* v,
+                                 float* dw, const HeadfitPlan& p, int pn, int ldg, hipStream_t s) {
+    u.x = x;
+    u.g = g;
+    u.w = w;
+    u.m = m;
+    u.v = v;
+    u.dw = dw;
+    u.n_items = p.update_items(pn);
+    u.R = (int32_t)p.rows;
+    u.K = p.F;
+    u.k_groups = p.k_groups;
+    u.C = p.C;
+    u.tile0 = p.panel_first_tile(pn);
+    u.panel_cols = ldg;
+    u.f_groups = p.f_groups;
+    return launch(adam ? headfit_update_kernel<true> : headfit_update_kernel<false>, dim3(p.update_grid(pn)), dim3(p.block), 0, s, u);
+}
+
+// The head of a step, for both fits, on the p.rows = B + Bg rows of x (p.F wide) and the packed w with its moments:
+// per class panel the logit gradient into g, the fold of its row sums (with loss3), `between(pn, tile0, n_tiles)` -
+// what the caller enqueues on a panel's G before w changes - and (HEADFIT_STEP: Adam with `u`'s scalars; HEADFIT_GRAD:
+// dW stored) the update; then the loss scalars.  `steps`: counted once the panels are enqueued, or null.
+template <typename Between>
+static int headfit_head_pass(int what, const HeadfitPlan& p, const float* x, float* w, float* m, float* v, float* g, float* parts,
+                             float* rowsum, const int32_t* labels, int32_t B, int32_t Bg, double weight, const HeadfitUpdateArgs& u,
+                             float* dW, float* loss3, int64_t* steps, hipStream_t s, Between&& between) {
+    const int32_t R = (int32_t)p.rows;
+    const double bc = (double)B * p.C;
+    for (int pn = 0; pn < p.n_panels; ++pn) {
+        HeadfitGradArgs a{};
+        a.x = x;
+        a.w4 = reinterpret_cast<const float4*>(w);
+        a.labels = labels;
+        a.g = g;
+        a.parts = parts;
+        a.n_items = p.grad_items(pn);
+        a.R = R;
+        a.B = B;
+        a.K = p.F;
+        a.k_groups = p.k_groups;
+        a.ld = p.ld;
+        a.C = p.C;
+        a.tile0 = p.panel_first_tile(pn);
+        a.n_tiles = p.panel_n_tiles(pn);
+        a.n_chunks = p.grad_chunks(pn);
+        a.panel_tiles = p.panel_tiles;
+        a.panel_cols = p.panel_cols;
+        a.s_neg = (float)(1.0 / bc);
+        a.s_lab = (float)(-(double)p.C / bc);
+        a.s_bg = Bg ? (float)(weight / ((double)Bg * p.C)) : 0.0f;
+        if (int rc = launch(headfit_grad_kernel_for(p.m_tiles, what != HEADFIT_LOSS), dim3(p.grad_grid(pn)), dim3(p.block), p.lds_bytes, s, a))
+            return rc;
+        if (loss3)
+            if (int rc = launch(headfit_fold_kernel, dim3(p.row_grid), dim3(p.block), 0, s, (const float*)parts, rowsum, R, a.n_tiles,
+                                a.panel_tiles, (int32_t)(pn == 0)))
+                return rc;
+        if (what == HEADFIT_LOSS) continue;
+        if (int rc = between(pn, a.tile0, a.n_tiles)) return rc;
+        if (int rc = headfit_update_launch(what == HEADFIT_STEP, u, x, g, w, m, v, dW, p, pn, p.panel_cols, s)) return rc;
+    }
+    if (steps) ++*steps;
+    if (!loss3) return RANGE_OK;
+    return launch(headfit_loss_kernel, dim3(1), dim3(p.block), 0, s, (const float*)rowsum, R, B, (int32_t)p.C, (float)weight, loss3);
+}
+
+// One call on the step's rows: the gather, then the head pass.
 static int headfit_run(range_ctx* c, int what, const float* feats, int64_t N, const int32_t* rows, const int32_t* labels,
                        int32_t B, const float* bg, int32_t Bg, double weight, const HeadfitAdam* adam, float* dW, float* loss3,
                        int64_t max_grid, int32_t panel_cols, range_stream_t stream) {
@@ -40,11 +121,7 @@ static int headfit_run(range_ctx* c, int what, const float* feats, int64_t N, co
     if (!h.C) return fail(RANGE_ERR_STATE, "no class-head fit begun (range_headfit_begin)");
     if (what == HEADFIT_GRAD && !dW) return fail(RANGE_ERR_INVALID, "null argument");
     if (what == HEADFIT_LOSS && !loss3) return fail(RANGE_ERR_INVALID, "null argument");
-    if (N < 1 || B < 1 || Bg < 0) return fail(RANGE_ERR_INVALID, "N and B must be > 0, Bg >= 0");
-    if ((bg != nullptr) != (Bg > 0)) return fail(RANGE_ERR_INVALID, "Bg = %d %s background rows", Bg, bg ? "with" : "without");
-    if (!rows && N < B) return fail(RANGE_ERR_INVALID, "B = %d rows without row ids: the feature matrix has %lld", B, (long long)N);
-    if (N > (INT64_C(1) << 40)) return fail(RANGE_ERR_INVALID, "N beyond 2^40");
-    if (!std::isfinite(weight)) return fail(RANGE_ERR_INVALID, "rand_sample_weight must be finite");
+    if (int rc = headfit_check_rows(N, rows, B, bg, Bg, weight, false)) return rc;
     if (!aligned(feats, 4) || !aligned(rows, 4) || !aligned(labels, 4) || !aligned(bg, 4) || !aligned(dW, 4) || !aligned(loss3, 4))
         return fail(RANGE_ERR_INVALID, "the device pointers must be 4-byte aligned");
     const int64_t R = (int64_t)B + Bg;
@@ -63,57 +140,8 @@ static int headfit_run(range_ctx* c, int what, const float* feats, int64_t N, co
     const hipStream_t s = (hipStream_t)stream;
     if (int rc = launch(headfit_gather_kernel, dim3(p.gather_grid), dim3(p.block), 0, s, feats, N, rows, B, bg, (int32_t)R, (int32_t)h.F, x))
         return rc;
-    const double bc = (double)B * h.C;
-    for (int pn = 0; pn < p.n_panels; ++pn) {
-        HeadfitGradArgs a{};
-        a.x = x;
-        a.w4 = reinterpret_cast<const float4*>(h.d_w.p);
-        a.labels = labels;
-        a.g = g;
-        a.parts = parts;
-        a.n_items = p.grad_items(pn);
-        a.R = (int32_t)R;
-        a.B = B;
-        a.K = h.F;
-        a.k_groups = p.k_groups;
-        a.ld = p.ld;
-        a.C = h.C;
-        a.tile0 = p.panel_first_tile(pn);
-        a.n_tiles = p.panel_n_tiles(pn);
-        a.n_chunks = p.grad_chunks(pn);
-        a.panel_tiles = p.panel_tiles;
-        a.panel_cols = p.panel_cols;
-        a.s_neg = (float)(1.0 / bc);
-        a.s_lab = (float)(-(double)h.C / bc);
-        a.s_bg = Bg ? (float)(weight / ((double)Bg * h.C)) : 0.0f;
-        if (int rc = launch(headfit_grad_kernel_for(p.m_tiles, what != HEADFIT_LOSS), dim3(p.grad_grid(pn)), dim3(p.block), p.lds_bytes, s, a))
-            return rc;
-        if (loss3)
-            if (int rc = launch(headfit_fold_kernel, dim3(p.row_grid), dim3(p.block), 0, s, (const float*)parts, rowsum, (int32_t)R,
-                                a.n_tiles, a.panel_tiles, (int32_t)(pn == 0)))
-                return rc;
-        if (what == HEADFIT_LOSS) continue;
-        u.x = x;
-        u.g = g;
-        u.w = h.d_w.p;
-        u.m = h.d_m.p;
-        u.v = h.d_v.p;
-        u.dw = dW;
-        u.n_items = p.update_items(pn);
-        u.R = (int32_t)R;
-        u.K = h.F;
-        u.k_groups = p.k_groups;
-        u.C = h.C;
-        u.tile0 = a.tile0;
-        u.panel_cols = p.panel_cols;
-        u.f_groups = p.f_groups;
-        if (int rc = launch(what == HEADFIT_STEP ? headfit_update_kernel<true> : headfit_update_kernel<false>, dim3(p.update_grid(pn)),
-                            dim3(p.block), 0, s, u))
-            return rc;
-    }
-    if (what == HEADFIT_STEP) ++h.steps;
-    if (!loss3) return RANGE_OK;
-    return launch(headfit_loss_kernel, dim3(1), dim3(p.block), 0, s, (const float*)rowsum, (int32_t)R, B, (int32_t)h.C, (float)weight, loss3);
+    return headfit_head_pass(what, p, x, h.d_w.p, h.d_m.p, h.d_v.p, g, parts, rowsum, labels, B, Bg, weight, u, dW, loss3,
+                             what == HEADFIT_STEP ? &h.steps : nullptr, s, [](int, int, int) { return RANGE_OK; });
 }
 
 extern "C" {

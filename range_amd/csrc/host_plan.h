@@ -730,6 +730,11 @@ constexpr int CSP_NTILE = 32;             // output columns of one MFMA tile
 constexpr int CSP_ACC_TILES = 8;          // 32x32 accumulator tiles of a wave: m_tiles * (n tiles of the wave)
 constexpr int64_t CSP_MAX_GRID = 2048;    // workgroups of a launch (one fits a CU); more tiles are walked grid-stride
 
+// The grid of a launch over `items`: at most CSP_MAX_GRID workgroups, or the smaller cap `max_grid` (0: none).
+inline unsigned csp_grid_cap(int64_t items, int64_t max_grid) {
+    return (unsigned)std::min(items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID);
+}
+
 struct CspLayerPlan {
     int in = 0, out = 0;                 // true widths
     int k_groups = 0, n_tiles = 0;       // ceil(in / CSP_KGROUP), ceil(out / CSP_NTILE)
@@ -792,7 +797,7 @@ inline CspPlan csp_plan(int kind, int F, int n_layers, const int* widths, bool s
     p.ld = (widest + CSP_NTILE - 1) / CSP_NTILE * CSP_NTILE + 1;
     p.lds_bytes = (size_t)p.tile_rows * p.ld * sizeof(float);
     p.n_tiles = (B + p.tile_rows - 1) / p.tile_rows;
-    p.grid = (unsigned)std::min(p.n_tiles, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID);
+    p.grid = csp_grid_cap(p.n_tiles, max_grid);
     p.valid = true;
     return p;
 }
@@ -903,7 +908,7 @@ inline CspHeadPlan csp_head_plan(int num_filts, int num_classes, int64_t M, int6
     // X tile, and (SUM) the four waves' partial row sums
     p.lds_bytes = ((size_t)p.tile_rows * p.ld + (size_t)4 * p.tile_rows) * sizeof(float);
     p.packed_floats = (size_t)p.n_tiles * CSP_NTILE * p.k_groups * CSP_KGROUP;
-    p.grid = (unsigned)std::min(p.n_items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID);
+    p.grid = csp_grid_cap(p.n_items, max_grid);
     p.valid = true;
     return p;
 }
@@ -984,7 +989,7 @@ inline CspRankPlan csp_rank_plan(int num_filts, int num_classes, int64_t B, int 
                             : (int)std::min<int64_t>(p.n_chunks, (CSP_RANK_TARGET_WG + p.row_tiles - 1) / p.row_tiles);
     p.n_items = p.row_tiles * p.col_parts;
     p.lds_bytes = (has_head ? (size_t)p.tile_rows * p.ld * sizeof(float) : 0) + (size_t)p.tile_rows * CSP_RANK_ROW_STATE;
-    p.grid = (unsigned)std::min(p.n_items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID);
+    p.grid = csp_grid_cap(p.n_items, max_grid);
     if (p.col_parts > 1) {
         p.ws_bytes = (size_t)p.col_parts * (size_t)B * CSP_RANK_WS_ROW;
         p.merge_grid = (unsigned)std::min<int64_t>((B + CSP_BLOCK - 1) / CSP_BLOCK, CSP_MAX_GRID);
@@ -1393,7 +1398,7 @@ struct HeadfitPlan {
     unsigned row_grid = 0;               // of the per-row kernels (fold)
     unsigned gather_grid = 0, unpack_grid = 0;
     int block = CSP_BLOCK;
-    unsigned cap(int64_t items) const { return (unsigned)std::min(items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID); }
+    unsigned cap(int64_t items) const { return csp_grid_cap(items, max_grid); }
     // panel p: its first class tile, its tiles
     int panel_first_tile(int p) const { return p * panel_tiles; }
     int panel_n_tiles(int p) const { return std::min(panel_tiles, n_tiles - p * panel_tiles); }
@@ -1486,7 +1491,7 @@ struct CspfitPlan {
     size_t lds_bytes = 0;                // the largest of the launches
     unsigned feat_grid = 0, row_grid = 0;
     int block = CSP_BLOCK;
-    unsigned cap(int64_t items) const { return (unsigned)std::min(items, max_grid ? std::min(max_grid, CSP_MAX_GRID) : CSP_MAX_GRID); }
+    unsigned cap(int64_t items) const { return csp_grid_cap(items, max_grid); }
     int in(int l) const { return net.layer[l].in; }
     int out(int l) const { return net.layer[l].out; }
     // layer l's forward product: the head's LOGITS launch on (rows, in) x (out, in)^T

@@ -91,6 +91,54 @@ def _labels(labels, n: int, num_classes: Optional[int]) -> Tuple[np.ndarray, int
     return lab.astype(np.int64), C
 
 
+def _locs64(locs, what: str) -> np.ndarray:
+    """``locs`` as a contiguous (n, 2) float64 array of finite (lon, lat) degrees; ``what`` names them in the refusals."""
+    a = locs.detach().cpu().numpy() if torch.is_tensor(locs) else np.asarray(locs)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"{what}: (n, 2) lon / lat degrees, got {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: non-finite entries")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _run_epochs(step: Callable, val_loss: Optional[Callable], n_val: int, N: int, lab: np.ndarray, dev, *, epochs: int,
+                batch_size: int, batches, balanced: bool, max_num_exs_per_class: int, lr: float, lr_decay: float,
+                rng: np.random.Generator, logger) -> Tuple[List[float], Optional[List[float]]]:
+    """The epochs of a fit - this module's and csp_fit.py's: per epoch the batches (``batches[epoch]``, or the sampler
+    on ``rng``), ``step(row ids on the GPU, spec, the epoch's lr)`` -> its (3,) loss scalars for each - it draws the
+    step's negatives from ``rng``, behind the sampler's draw -, the mean of the losses weighted by rows, the same of
+    ``val_loss(i, j)`` over the ``n_val`` validation rows in slices of ``batch_size`` (or no ``val_loss``), and the
+    logger's line.  -> (train losses, validation losses or None)."""
+    from ._headfit_native import MAX_ROWS
+    train_losses, val_losses = [], ([] if val_loss is not None else None)
+    for epoch in range(epochs):
+        if batches is not None:
+            plan = [(np.asarray(r, dtype=np.int64), spec) for r, spec in batches[epoch]]
+        else:
+            idx = balanced_indices(lab, max_num_exs_per_class, rng) if balanced else rng.permutation(N)
+            plan = [(idx[i:i + batch_size], None) for i in range(0, len(idx), batch_size)]
+        losses, sizes = [], []
+        for rows, spec in plan:
+            if rows.ndim != 1 or not 1 <= len(rows) <= MAX_ROWS or rows.min() < 0 or rows.max() >= N:
+                raise ValueError(f"a batch's row ids: 1 .. {MAX_ROWS} integers in 0 .. {N - 1}")
+            losses.append(step(torch.from_numpy(rows.astype(np.int32)).to(dev), spec, lr * lr_decay ** epoch))
+            sizes.append(len(rows))
+        per_step = torch.stack(losses)[:, 0].double().cpu().numpy()
+        train_losses.append(float(np.average(per_step, weights=np.asarray(sizes, dtype=np.float64))))
+        if val_loss is not None:
+            vs, vn = [], []
+            for i in range(0, n_val, batch_size):
+                j = min(n_val, i + batch_size)
+                vs.append(val_loss(i, j))
+                vn.append(j - i)
+            v = torch.stack(vs)[:, 2].double().cpu().numpy()
+            val_losses.append(float(np.average(v, weights=np.asarray(vn, dtype=np.float64))))
+        if logger is not None:
+            logger.info("Epoch {}\tLoss  : {:.4f}".format(epoch, train_losses[-1]) +
+                        ("\tTest loss   : {:.4f}".format(val_losses[-1]) if val_loss is not None else ""))
+    return train_losses, val_losses
+
+
 def fit_head_on_features(feats_dev: torch.Tensor, labels, bg_feats_fn: Callable, num_classes: Optional[int] = None, *,
                          engine=None, epochs: int = 30, batch_size: int = 1024, lr: float = 1e-3, lr_decay: float = 0.98,
                          weight_decay: float = 0.0, rand_sample_weight: float = 1.0, max_num_exs_per_class: int = 100,
@@ -127,35 +175,15 @@ def fit_head_on_features(feats_dev: torch.Tensor, labels, bg_feats_fn: Callable,
         val_feats = val[0].contiguous()
         vl, _ = _labels(val[1], val_feats.shape[0], C)
         val_lab = torch.from_numpy(vl.astype(np.int32)).to(dev)
-    train_losses, val_losses = [], ([] if val is not None else None)
-    for epoch in range(epochs):
-        if batches is not None:
-            plan = [(np.asarray(r, dtype=np.int64), spec) for r, spec in batches[epoch]]
-        else:
-            idx = balanced_indices(lab, max_num_exs_per_class, rng) if balanced else rng.permutation(N)
-            plan = [(idx[i:i + batch_size], None) for i in range(0, len(idx), batch_size)]
-        losses, sizes = [], []
-        for rows, spec in plan:
-            if rows.ndim != 1 or not 1 <= len(rows) <= MAX_ROWS or rows.min() < 0 or rows.max() >= N:
-                raise ValueError(f"a batch's row ids: 1 .. {MAX_ROWS} integers in 0 .. {N - 1}")
-            rows_dev = torch.from_numpy(rows.astype(np.int32)).to(dev)
-            bg = bg_feats_fn(len(rows), spec, rng)
-            losses.append(fit.step(feats_dev, rows_dev, lab_dev[rows_dev.long()], bg, lr * lr_decay ** epoch,
-                                   weight=rand_sample_weight, weight_decay=weight_decay))
-            sizes.append(len(rows))
-        per_step = torch.stack(losses)[:, 0].double().cpu().numpy()
-        train_losses.append(float(np.average(per_step, weights=np.asarray(sizes, dtype=np.float64))))
-        if val is not None:
-            vs, vn = [], []
-            for i in range(0, val_feats.shape[0], batch_size):
-                j = min(val_feats.shape[0], i + batch_size)
-                vs.append(fit.loss(val_feats[i:j], None, val_lab[i:j], None))
-                vn.append(j - i)
-            v = torch.stack(vs)[:, 2].double().cpu().numpy()
-            val_losses.append(float(np.average(v, weights=np.asarray(vn, dtype=np.float64))))
-        if logger is not None:
-            logger.info("Epoch {}\tLoss  : {:.4f}".format(epoch, train_losses[-1]) +
-                        ("\tTest loss   : {:.4f}".format(val_losses[-1]) if val is not None else ""))
+
+    def step(rows_dev, spec, lr_epoch):
+        bg = bg_feats_fn(len(rows_dev), spec, rng)
+        return fit.step(feats_dev, rows_dev, lab_dev[rows_dev.long()], bg, lr_epoch, weight=rand_sample_weight, weight_decay=weight_decay)
+
+    train_losses, val_losses = _run_epochs(
+        step, None if val is None else lambda i, j: fit.loss(val_feats[i:j], None, val_lab[i:j], None),
+        0 if val is None else val_feats.shape[0], N, lab, dev, epochs=epochs, batch_size=batch_size, batches=batches, balanced=balanced,
+        max_num_exs_per_class=max_num_exs_per_class, lr=lr, lr_decay=lr_decay, rng=rng, logger=logger)
     return HeadFitResult(fit.weights().cpu().numpy(), train_losses, val_losses, fit.steps)
 
 
@@ -178,12 +206,7 @@ def fit_class_head(model, train_locs, train_classes, num_classes: Optional[int] 
     dev = eng.device
 
     def embed(locs) -> torch.Tensor:
-        a = locs.detach().cpu().numpy() if torch.is_tensor(locs) else np.asarray(locs)
-        if a.ndim != 2 or a.shape[1] != 2:
-            raise ValueError(f"locations: (n, 2) lon / lat degrees, got {a.shape}")
-        if not np.isfinite(a).all():
-            raise ValueError("locations: non-finite entries")
-        return loc_model.encode(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev))
+        return loc_model.encode(torch.from_numpy(_locs64(locs, "locations")).to(dev))
 
     if isinstance(init, str) and init == "checkpoint":
         head = getattr(loc_model.loc_enc, "class_emb", None)

@@ -4,7 +4,8 @@ there; tests/test_cspfit_cpu.py holds the reference's own float32 results to the
 
 Every fixture case; the smallest shapes where a tile can go wrong (rows 1 / 31 / 32 / 33 / 65 with Bg = 0 and with B = 1,
 widths 1 / 31 / 33 / 96 / 513, F = 1, an in0 that is no multiple of 8, C of 1 / 33 / 70 in panels of 32, row ids given,
-repeated and absent, a label outside 0 .. C - 1); bits across grid caps, streams and panel widths; a step against Adam
+repeated and absent, a label outside 0 .. C - 1); bits across grid caps, streams and panel widths; the head against the class-head fit on the same embeddings, bit for
+bit; a step against Adam
 restated on the gradient launch's bits; the training forward against range_csp_encode; dropout; the six-step
 trajectories, re-anchored at the GPU's own parameters step by step; saturated pre-activations, saturated logits and a NaN
 location; refusals; a planted task at model level; and fit_location_model against the restatement of its whole loop."""
@@ -19,6 +20,7 @@ import csp_refs
 import cspfit_cases as K
 import cspfit_refs as R
 from range_amd import _cspfit_native as cn
+from range_amd import _headfit_native as hn
 from range_amd import _native, csp, csp_fit, head_fit
 from tools import synth
 
@@ -166,6 +168,37 @@ def test_bits_after_three_steps_across_grids_panels_and_streams(fit, golden):
     s.synchronize()
     for a, c in zip(want, got):
         assert torch.equal(a, c), "another stream"
+
+
+#: (spa, F, hidden, layers, num_filts, act, layn, B, Bg, C, panel_cols): three panels of 32 classes with the last ragged, a
+#: ragged 32-row tile and a K that is no multiple of 8; then one class, rows over two tiles, no background, one panel
+HEAD_SHAPES = [("gridcell", 3, 12, 2, 33, "tanh", True, 33, 31, 70, 32), ("gridcell", 8, 32, 2, 96, "gelu", False, 65, 0, 1, 0)]
+
+
+@pytest.mark.parametrize("shape", HEAD_SHAPES, ids=lambda s: "nf%d_C%d_B%d_Bg%d_panel%d" % (s[4], s[9], s[7], s[8], s[10]))
+def test_head_of_a_csp_fit_is_the_head_fit(fit, tmp_path, shape):
+    """The head of a CSP fit is the class-head fit on the CSP fit's embeddings, bit for bit - gradient, loss scalars and
+    an Adam step: both run the one head pass of headfit_host.h.  No tolerance anywhere."""
+    spa, F, hidden, layers, nf, act, layn, B, Bg, C, panel_cols = shape
+    p = make_net(tmp_path, spa, F, hidden, layers, nf, act, layn, C, seed=900 + nf)
+    d = on_gpu(batch(B, Bg, C, seed=B + C))
+    weight, adam = 0.75, dict(lr=1e-2, weight_decay=0.01)
+    fit.begin(p, C, p.class_emb)
+    _, emb = fit.loss(*d, weight, want_emb=True)
+    flat, l3 = fit.grad(*d, weight, panel_cols=panel_cols)
+    if panel_cols:
+        assert cn.plan(p.kind, F, p.widths, True, layn, C, B + Bg, 0, panel_cols)["n_panels"] == 3
+    head = hn.HeadFit(DEV)
+    head.begin(C, nf, p.class_emb)
+    rows = (emb[:B], None, d[2], emb[B:] if Bg else None)
+    dW, l3h = head.grad(*rows, weight, panel_cols=panel_cols)
+    assert torch.equal(dW, cn.split_unpacked(flat, p, C)["class_emb"]) and torch.equal(l3h, l3)
+    fit.step(*d, weight=weight, panel_cols=panel_cols, **adam)
+    head.step(*rows, weight=weight, panel_cols=panel_cols, **adam)
+    assert (fit.steps, head.steps) == (1, 1)
+    W = head.weights()
+    assert torch.equal(W, cn.split_unpacked(fit.flat_params(), p, C)["class_emb"])
+    assert not torch.equal(W.cpu(), torch.from_numpy(np.ascontiguousarray(p.class_emb, dtype=np.float32)))
 
 
 @pytest.mark.parametrize("case,wd", (("gelu_ln_skip", 0.0), ("relu_theory", 0.01)))
