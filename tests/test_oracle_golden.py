@@ -28,8 +28,10 @@ def test_sh_and_encoder_vs_reference(tag):
     z = np.load(os.path.join(GOLDEN, tag + ".npz"))
     q, L, mode = z["lonlat"], int(z["L"]), str(z["mode"])
     Y = O.sh_features(q, L, mode)
-    rows = z["sh_rows"]
-    d = np.abs(Y[rows] - z["sh_features"]).max(axis=1)
+    # (the fixtures beyond L = 40 - make_golden_enc_sweep.py - hold the embedding only: 4096 features a row are too many)
+    rows = z["sh_rows"] if "sh_rows" in z.files else np.zeros(0, dtype=np.int64)
+    assert len(rows) > 0 or L > 40
+    d = np.abs(Y[rows] - z["sh_features"]).max(axis=1) if len(rows) else np.zeros(1)
     lat = np.abs(q[rows, 1])
     w = synth.make_encoder_weights(L, int(z["hidden"]), 256, int(z["num_hidden_layers"]),
                                    int(z["seed"]))
